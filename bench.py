@@ -20,6 +20,11 @@ Other workloads (--workload):
   stream  config 4: per scan, match against the latest map + local-map insert
           + latest-map rebuild from the last 10 scans (replicas)
 
+A plain run sets up, warms up, times --steps steps and prints the line.
+--full adds everything measured beside the headline (CPU baselines, the
+lone-call latency, the one-stream kernel pass, the other configurations'
+sub-lines); --dump-outputs DIR writes the last timed step's outputs as .npy.
+
 Rank 0 prints ONE JSON line (DESIGN.md §6 explains every field).
 """
 from __future__ import annotations
@@ -55,6 +60,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=None, help="default: 200 (match/refine), 4 (loop), 500 (stream)")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", default="match", choices=["match", "refine", "loop", "loop_bb", "stream", "rebuild"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baselines, the lone-call latency, "
+                         "the one-stream kernel pass, the sub-lines of the other configurations (--no-cpu, "
+                         "--latency-calls, --loop-line, --dropin-line and --sub-lines choose among them).  Without "
+                         "it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as "
+                         "DIR/<name>.npy (float64; at most 64 MB in all, a seeded sample of anything larger)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline budget")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--spin-sync", type=int, default=1, help="1 spin on the stream when waiting, 0 blocking wait")
@@ -116,7 +129,38 @@ def parse():
     d_warm = dict(match=10, refine=5, loop=1, loop_bb=2, stream=10, rebuild=2)[a.workload]
     a.steps = d_steps if a.steps is None else a.steps
     a.warmup = d_warm if a.warmup is None else a.warmup
+    if not a.full:   # a plain run: nothing beside the headline's timed region
+        a.no_cpu, a.latency_calls, a.loop_line, a.dropin_line, a.sub_lines = True, 0, 0, 0, 0
     return a
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> what the timed path returned in its
+    last timed step) as <path>/<name>.npy in float64.  Past 64 MB in all, every
+    array is cut to a fixed seeded sample of its elements (sorted indices)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    header = 256 * len(arrays)   # .npy headers (128 B each for these shapes), with room to spare
+    data = sum(a.nbytes for a in arrays.values())
+    rng = np.random.default_rng(0)
+    for name, a in sorted(arrays.items()):
+        if data + header > DUMP_CAP_BYTES:
+            keep = max(1, int(a.size * (DUMP_CAP_BYTES - header) / data))
+            a = a.ravel()[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def summaries_arrays(outs):
+    """The fields of a list of match summaries a caller reads, one row per query."""
+    return dict(pose_found=[o.pose_found for o in outs],
+                estimated_pose=[o.estimated_pose.tuple() for o in outs],
+                normalized_cost=[o.normalized_cost for o in outs],
+                covariance=[list(o.covariance) for o in outs],
+                score_max=[o.score_max for o in outs],
+                best_win=[list(o.best_win) for o in outs])
 
 
 class Dist:
@@ -528,6 +572,7 @@ def run_match(args, D, ctx):
                          sum(1 << abi.KERNEL_IDS.index(k) for k in args.skip_kernels.split(",")))
     results = np.zeros((args.steps * B, 7))
     lat = [[] for _ in range(S)]
+    last = {}
 
     def stream(i):
         c, g, ds = state[i]
@@ -535,6 +580,8 @@ def run_match(args, D, ctx):
             ts = time.perf_counter()
             outs, js = call(c, g, ds, args.warmup + k)
             lat[i].append(time.perf_counter() - ts)
+            if k == args.steps - 1:
+                last["outs"] = outs
             for q, (out, j) in enumerate(zip(outs, js)):
                 e = out.estimated_pose
                 results[k * B + q] = (e.x, e.y, e.theta, out.score_max, out.coarse_blocks, out.fine_blocks, j)
@@ -567,21 +614,23 @@ def run_match(args, D, ctx):
         ts = time.perf_counter()
         c0.optimize_pose_query(g0[0] if isinstance(g0, list) else g0, P, cost, ds0[j], inits[j])
         lat1.append(time.perf_counter() - ts)
-    c0.set_option(abi.LGS_OPT_PROFILE, 1)
-    c0.set_option(abi.LGS_OPT_DEVICE_TIMING, 1 if args.device_timing else 0)
-    # one stream: a chunk's tail on the priority stream would overlap the next
-    # chunk's plane builds, and the table is of kernels alone
-    prio = 1 if "28=1" in os.environ.get("LGS_CTX_OPTIONS", "") else 0   # the timed region's setting
-    c0.set_option(abi.LGS_OPT_PRIORITY_TAIL, 0)
-    c0.reset_stats()
-    iso_calls = min(max(1, 1024 // B), args.steps)   # ~16 coarse launches
-    for k in range(iso_calls):
-        call(c0, g0, ds0, args.warmup + k)
-    all_stats = c0.kernel_stats()
-    c0.set_option(abi.LGS_OPT_PROFILE, 0)
-    c0.set_option(abi.LGS_OPT_PRIORITY_TAIL, prio)
-    if "k_coarse" not in stats:
-        stats = all_stats
+    all_stats = None
+    if args.full:
+        c0.set_option(abi.LGS_OPT_PROFILE, 1)
+        c0.set_option(abi.LGS_OPT_DEVICE_TIMING, 1 if args.device_timing else 0)
+        # one stream: a chunk's tail on the priority stream would overlap the next
+        # chunk's plane builds, and the table is of kernels alone
+        prio = 1 if "28=1" in os.environ.get("LGS_CTX_OPTIONS", "") else 0   # the timed region's setting
+        c0.set_option(abi.LGS_OPT_PRIORITY_TAIL, 0)
+        c0.reset_stats()
+        iso_calls = min(max(1, 1024 // B), args.steps)   # ~16 coarse launches
+        for k in range(iso_calls):
+            call(c0, g0, ds0, args.warmup + k)
+        all_stats = c0.kernel_stats()
+        c0.set_option(abi.LGS_OPT_PROFILE, 0)
+        c0.set_option(abi.LGS_OPT_PRIORITY_TAIL, prio)
+        if "k_coarse" not in stats:
+            stats = all_stats
     err = [max(abs(results[k, 0] - truths[int(results[k, 6])][0]),
                abs(results[k, 1] - truths[int(results[k, 6])][1])) for k in range(args.steps * B)]
     cpu = None
@@ -649,15 +698,18 @@ def run_match(args, D, ctx):
                 "avg_launch_ms dispatch-inclusive, execution = first start to last end"
                 if args.device_timing else "HIP events on each launch's stream"),
         timed_region_kernels=trk, largest_kernel=top,
-        roofline_isolated=roofline_from(all_stats, "k_coarse", args.pmc, "k_coarse_list", "l2-gather"),
-        coarse_stage=coarse_stage(all_stats),
+        # (the one-stream pass: --full)
+        roofline_isolated=(roofline_from(all_stats, "k_coarse", args.pmc, "k_coarse_list", "l2-gather")
+                           if all_stats else None),
+        coarse_stage=coarse_stage(all_stats) if all_stats else None,
         pose_err_max_m=round(float(max(err)), 4), timed_events=args.timed_events,
         super_prune=bool(args.super_prune),
         coarse_blocks_scored_mean=round(float(results[:, 4].mean()), 1),
         fine_blocks_refined_mean=round(float(results[:, 5].mean()), 1))
+    line["_outputs"] = summaries_arrays(last.get("outs", []))
     for c in ctxs[1:]:
         c.close()
-    return line, all_stats, value
+    return line, all_stats if all_stats else stats, value
 
 
 # -------------------------------------------------------------------- refine
@@ -674,13 +726,13 @@ def run_refine(args, D, ctx):
     for k in range(args.warmup):
         ctx.linsolve(grid, lp, dscans[k % len(dscans)], inits[k % len(dscans)])
     set_timed_events(ctx, args, "k_linsolve")
-    lat = []
+    lat, last = [], None
     D.barrier()
     t0 = time.perf_counter()
     for k in range(args.steps):
         j = (args.warmup + k) % len(dscans)
         ts = time.perf_counter()
-        ctx.linsolve(grid, lp, dscans[j], inits[j])
+        last = ctx.linsolve(grid, lp, dscans[j], inits[j])
         lat.append(time.perf_counter() - ts)
     elapsed = D.max(time.perf_counter() - t0)
     stats = ctx.kernel_stats()
@@ -691,9 +743,11 @@ def run_refine(args, D, ctx):
         tb = time.perf_counter()
         ctx.linsolve_batch(grid, lp, dscans[:nb], inits[:nb])
         return nb / (time.perf_counter() - tb)
-    batch_rate = batch_rate_of(min(64, len(dscans)))
-    # a batch that fills the device: one 512-thread workgroup per refine, one per CU
-    batch_rate_full = batch_rate_of(min(256, len(dscans)))
+    batch_rate = batch_rate_full = None
+    if args.full:
+        batch_rate = batch_rate_of(min(64, len(dscans)))
+        # a batch that fills the device: one 512-thread workgroup per refine, one per CU
+        batch_rate_full = batch_rate_of(min(256, len(dscans)))
     cpu = None
     if D.rank == 0 and not args.no_cpu and D.world == 1:
         ob = oracle_lib()
@@ -719,10 +773,14 @@ def run_refine(args, D, ctx):
         config=dict(workload="config3: Gauss-Newton refine (LinearSolver + CostSquareError), 50 iterations",
                     beams=1081, grid=[1000, 1000], iterations=50, parallelism=f"replicas x{D.world}"),
         p50_refine_ms=round(float(np.percentile(lat_ms, 50)), 4),
-        batched_refines_per_s_per_gpu=round(batch_rate, 1),
-        batched_refines_per_s_per_gpu_256=round(batch_rate_full, 1),
+        batched_refines_per_s_per_gpu=round(batch_rate, 1) if args.full else None,
+        batched_refines_per_s_per_gpu_256=round(batch_rate_full, 1) if args.full else None,
         roofline=None, cpu_baseline=cpu,
         kernel_avg_ms=round(k["total_ms"] / k["launches"], 5) if k.get("launches") else None)
+    if last is not None:
+        line["_outputs"] = dict(pose_found=[last.pose_found], iterations=[last.iterations],
+                                estimated_pose=[last.estimated_pose.tuple()], covariance=[list(last.covariance)],
+                                normalized_cost=[last.normalized_cost], cost=[last.cost])
     return line, stats, value
 
 
@@ -840,6 +898,13 @@ def run_loop(args, D, ctx):
         step_ms_p10_p50_p90=[round(1e3 * float(np.percentile(step_s, q)), 4) for q in (10, 50, 90)],
         step_spread=round(float((np.percentile(step_s, 90) - np.percentile(step_s, 10)) / np.median(step_s)), 4),
         cpu_baseline=cpu)
+    recs = loopbatch.decode(rec)   # every candidate's record of the last step, in candidate order
+    line["_outputs"] = dict(found=[r.found for r in recs],
+                            node_indices=[(r.start_node_index, r.end_node_index) for r in recs],
+                            relative_pose=[r.relative_pose.tuple() for r in recs],
+                            estimated_pose=[r.estimated_pose.tuple() for r in recs],
+                            covariance=[list(r.covariance) for r in recs], score=[r.score for r in recs],
+                            normalized_cost=[r.normalized_cost for r in recs])
     return line, stats, value
 
 
@@ -961,6 +1026,7 @@ def run_stream(args, D, ctx):
                     scan_interpolator=bool(args.interp), latest_map_scans=10, parallelism=f"replicas x{D.world}"),
         final_drift_m=round(float(drift), 4), breakdown_per_step=breakdown,
         roofline=roofline_from(stats, "k_ray_apply", args.pmc, "k_apply", "hbm", workload=args.workload), cpu_baseline=cpu)
+    line["_outputs"] = dict(estimated_poses=est)   # every step's pose; the last row is the last timed step's
     return line, stats, value
 
 
@@ -1075,6 +1141,7 @@ def run_stream_cpp(args, D, ctx):
         oracle_replay=replay, kernel_ms_per_step=kernel_ms_per_step,
         kernel_ms_per_step_note=f"HIP-event times of the {wsteps} untimed warmup steps (every kernel timed), per step",
         roofline=None, cpu_baseline=cpu)
+    line["_outputs"] = dict(estimated_poses=est)   # every step's pose; the last row is the last timed step's
     return line, stats, value
 
 
@@ -1150,10 +1217,18 @@ def run_rebuild(args, D, ctx):
     elapsed = D.max(time.perf_counter() - t0)
     stats = ctx.kernel_stats()
     ctx.set_option(abi.LGS_OPT_PROFILE, 0)
-    t1 = time.perf_counter()
-    gm = ctx.construct_global_map(0.05, 64, dscans, variants[0], bp)
-    global_ms = 1e3 * (time.perf_counter() - t1)
-    gg = gm.geometry()
+    outputs = {}
+    if args.dump_outputs:   # the local maps as the last timed step left them
+        for i, m in enumerate(maps):
+            cells, hits, misses = m.download()
+            outputs.update({f"map{i:02d}_cells": cells, f"map{i:02d}_hits": hits, f"map{i:02d}_misses": misses})
+    global_map = None
+    if args.full:
+        t1 = time.perf_counter()
+        gm = ctx.construct_global_map(0.05, 64, dscans, variants[0], bp)
+        global_ms = 1e3 * (time.perf_counter() - t1)
+        gg = gm.geometry()
+        global_map = dict(ms=round(global_ms, 3), cells=[gg["w"], gg["h"]], nodes=n_nodes)
     cpu = None
     if D.rank == 0 and not args.no_cpu and D.world == 1:
         ob = oracle_lib()
@@ -1177,8 +1252,9 @@ def run_rebuild(args, D, ctx):
         vs_baseline=None, dtype="f64", data="synthetic 400-node circular trajectory, pose corrections N(0, 3 cm)",
         config=dict(workload="f2: GridMapBuilder::AfterLoopClosure (all local maps, one fused ray-cast pass)",
                     nodes=n_nodes, local_maps=len(maps), beams=1081, parallelism=f"replicas x{D.world}"),
-        global_map=dict(ms=round(global_ms, 3), cells=[gg["w"], gg["h"]], nodes=n_nodes),
+        global_map=global_map,
         roofline=roofline_from(stats, "k_ray_apply", args.pmc, "k_apply", "hbm", workload=args.workload), cpu_baseline=cpu)
+    line["_outputs"] = outputs
     return line, stats, value
 
 
@@ -1190,10 +1266,10 @@ SUB_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def sub_line(args, D, ctx, workload, steps, warmup, cpu_seconds, **extra):
-    """Another workload's line inside the default run (its own steps, warmup
+    """Another workload's line inside the --full run (its own steps, warmup
     and bounded CPU baseline), with its per-kernel event times."""
     sa = argparse.Namespace(**vars(args))
-    sa.workload, sa.steps, sa.warmup, sa.cpu_seconds = workload, steps, warmup, cpu_seconds
+    sa.workload, sa.steps, sa.warmup, sa.cpu_seconds, sa.dump_outputs = workload, steps, warmup, cpu_seconds, None
     for k, v in extra.items():
         setattr(sa, k, v)
     fn = dict(refine=run_refine, stream=run_stream_cpp, rebuild=run_rebuild)[workload]
@@ -1230,6 +1306,9 @@ def main():
                           stream=run_stream_cpp if args.driver == "cpp" else run_stream,
                           rebuild=run_rebuild)[args.workload](
         args, D, ctx)
+    outputs = line.pop("_outputs", {})
+    if args.dump_outputs and D.rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     line["kernels"] = {k: dict(launches=v["launches"], avg_ms=round(v["total_ms"] / max(1, v["launches"]), 5))
                        for k, v in stats.items()}
     if args.workload == "match" and args.loop_line:

@@ -79,6 +79,42 @@ def test_roofline_dispatch_basis_with_execution(bench, tmp_path):
                                "k_coarse", "x", "k", "hbm", time_key="dispatch_ms") is None
 
 
+def test_plain_run_is_lean_and_full_keeps_the_side_lines(bench, monkeypatch):
+    """Without --full nothing beside the headline's timed region runs; with it
+    the side lines' options hold what they are given."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu and (a.latency_calls, a.loop_line, a.dropin_line, a.sub_lines) == (0, 0, 0, 0)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--loop-line", "0", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and not a.no_cpu and a.dump_outputs == "d"
+    assert (a.latency_calls, a.loop_line, a.dropin_line, a.sub_lines) == (100, 0, 1, 1)
+
+
+def test_dump_outputs(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy per name; past the cap, the same seeded
+    sample of every array from run to run, under the cap in all."""
+    import numpy as np
+    small = dict(pose=[(1.0, 2.0, 3.0)], found=np.array([1, 0], dtype=np.int32))
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert sorted(os.listdir(tmp_path / "a")) == ["found.npy", "pose.npy"]
+    pose = np.load(tmp_path / "a" / "pose.npy")
+    assert pose.dtype == np.float64 and pose.shape == (1, 3) and pose.tolist() == [[1.0, 2.0, 3.0]]
+    assert np.load(tmp_path / "a" / "found.npy").tolist() == [1.0, 0.0]
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4096)
+    big = dict(u=np.arange(1000.0), v=np.arange(3000.0).reshape(30, 100))
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    total = 0
+    for name in ("u", "v"):
+        b, c = np.load(tmp_path / "b" / f"{name}.npy"), np.load(tmp_path / "c" / f"{name}.npy")
+        assert b.tolist() == c.tolist() and 0 < b.size < big[name].size
+        assert np.all(np.diff(b) > 0)   # a sample of the elements, in order
+        total += os.path.getsize(tmp_path / "b" / f"{name}.npy")
+    assert total <= 4096
+
+
 def test_timed_region_ranking(bench):
     """largest_kernel: the chunk kernel with the largest share of the summed
     device-timed execution of the timed region."""

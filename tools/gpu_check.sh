@@ -19,8 +19,8 @@ step() {  # step <name> <timeout> <cmd...>
 }
 step pytest_gpu 900 python -m pytest tests -m gpu -x -q ${PYTEST_ARGS}
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py --steps ${BENCH_STEPS:-200} --warmup 10
+step bench 600 python bench.py --full --steps ${BENCH_STEPS:-200} --warmup 10
 if [ -n "$PROFILE" ]; then
-  step rocprof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run -- python bench.py --steps 50 --warmup 5 --no-cpu
+  step rocprof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run -- python bench.py --full --steps 50 --warmup 5 --no-cpu
 fi
 echo done

@@ -28,7 +28,7 @@ for ph in $PHASES; do
     find $OUT/trace_$TAG -name '*kernel_stats.csv' -exec cp {} $OUT/${TAG}_run_kernel_stats.csv \;
     rm -rf $OUT/pmc_fetch_$TAG $OUT/pmc_write_$TAG $OUT/pmc_l2_$TAG $OUT/trace_$TAG ;;
   bench)
-    tools/gpu_step.sh "bench|900|python -u bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err" || exit $?
+    tools/gpu_step.sh "bench|900|python -u bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err" || exit $?
     python3 -c "import json;d=json.loads(open('$OUT/${TAG}_bench.json').read().strip().splitlines()[-1]);print(d['value'], d['roofline']['frac'], d['roofline']['traffic'], [(k, (d.get(k) or {}).get('value')) for k in ('config5_strong_scaling','config4_stream','config3_refine','f2_rebuild','config2_distinct_maps')])" ;;
   esac
 done

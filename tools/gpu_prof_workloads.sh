@@ -10,7 +10,7 @@ OUT=gpurun_out
 TAG=${1:-r03_vX}; shift
 mkdir -p $OUT
 for w in ${@:-loop loop_bb rebuild}; do
-  BENCH="bench.py --workload $w --steps ${STEPS:-20} --warmup 2 --no-cpu"
+  BENCH="bench.py --full --workload $w --steps ${STEPS:-20} --warmup 2 --no-cpu"
   for pass in "trace --kernel-trace --stats" "pmc_fetch --pmc FETCH_SIZE" "pmc_write --pmc WRITE_SIZE" \
               "pmc_l2 --pmc TCC_HIT_sum TCC_MISS_sum"; do
     set -- $pass; name=$1; shift
@@ -27,7 +27,7 @@ for w in ${@:-loop loop_bb rebuild}; do
   cp $OUT/${TAG}_${w}_pmc.json profiles/pmc_summary_$w.json
   cp $OUT/${TAG}_${w}_pmc.json $OUT/pmc_summary_$w.json
   rm -rf $OUT/pmc_fetch_${TAG}_$w $OUT/pmc_write_${TAG}_$w $OUT/pmc_l2_${TAG}_$w $OUT/trace_${TAG}_$w
-  timeout -k 10 300 python -u bench.py --workload $w > $OUT/${TAG}_bench_$w.json 2> $OUT/${TAG}_bench_$w.err || exit $?
+  timeout -k 10 300 python -u bench.py --full --workload $w > $OUT/${TAG}_bench_$w.json 2> $OUT/${TAG}_bench_$w.err || exit $?
   python3 -c "import json;d=json.loads(open('$OUT/${TAG}_bench_$w.json').read().strip().splitlines()[-1]);print('$w', d['value'], d['unit'], d['roofline'])"
 done
 echo done
