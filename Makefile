@@ -17,6 +17,7 @@ oracle_ref:
 
 cpptest: host oracle
 	$(MAKE) -C tests/cpp
+	$(MAKE) -C tests/cpp_gs
 
 clean:
 	$(MAKE) -C my-lidar-graph-slam_amd/csrc clean
@@ -24,5 +25,6 @@ clean:
 	$(MAKE) -C oracle clean
 	$(MAKE) -C oracle/ref clean
 	$(MAKE) -C tests/cpp clean
+	$(MAKE) -C tests/cpp_gs clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean

@@ -55,6 +55,11 @@
  *   lgs_bb_optimize_pose_query   ScanMatcherBranchBound::OptimizePose(query) :29-44
  *   lgs_loop_detect_bb           LoopDetectorBranchBound::Detect + FindCorrespondingPose
  *                                C/mapping/loop_detector_branch_bound.cpp:26-117
+ *   lgs_gs_optimize_pose_batch   ScanMatcherGridSearch::OptimizePose(map, scan, pose, thr)
+ *                                C/mapping/scan_matcher_grid_search.cpp:44-114
+ *   lgs_gs_optimize_pose_query   ScanMatcherGridSearch::OptimizePose(query) :31-41
+ *   lgs_loop_detect_gs           LoopDetectorGridSearch::Detect + FindCorrespondingPose
+ *                                C/mapping/loop_detector_grid_search.cpp:26-106
  *
  * Threading: one lgs_ctx per matcher instance (the reference's frontend and
  * loop detector own distinct matchers, C/slam_launcher.cpp:774-775, :835).  A
@@ -588,6 +593,65 @@ int  lgs_bb_optimize_pose_query(lgs_ctx* ctx, const lgs_grid* grid, const lgs_bb
  * its local map (computed here; lgs_loop_query.coarse is ignored), then every
  * candidate matched with the score threshold.  One result per candidate. */
 int  lgs_loop_detect_bb(lgs_ctx* ctx, const lgs_bb_params* params, const lgs_cost_ge_params* cost,
+                        double score_threshold, const lgs_loop_query* queries, int num_queries,
+                        const lgs_loop_candidate* candidates, int num_candidates,
+                        lgs_loop_result* results);
+
+/* ---- exhaustive grid-search matcher ----
+ * ScanMatcherGridSearch (C/mapping/scan_matcher_grid_search.cpp:9-114,
+ * H/mapping/scan_matcher_grid_search.hpp) with ScorePixelAccurate
+ * (C/mapping/score_function_pixel_accurate.cpp:19-77).  Every pose
+ * (sp.x + dx, sp.y + dy, sp.theta + dt), sp = Compound(initialPose,
+ * relativeSensorPose), of the window is scored on the device; the offsets are
+ * the values of the reference's `for (double d = -range / 2; d <= range / 2;
+ * d += step)` loops (lgs_gs_steps), dy outermost, dt innermost; the result is
+ * the first pose in that order of the maximum score, if that maximum is > the
+ * threshold.  Field order follows the constructor (rangeX,
+ * rangeY, rangeTheta, stepX, stepY, stepTheta) then ScorePixelAccurate
+ * (usableRangeMin, usableRangeMax).
+ * Caps (LGS_ERR_INVALID_ARG beyond them): 4096 values per window axis, 2^24
+ * poses per window, 2 GiB of index tables per match (4 B x angles x valid
+ * beams x (x values + y values), plus 16 B x angles x valid beams), maps of
+ * fewer than 2^30 cells.  A call of many matches runs in chunks whose tables
+ * fit 1 GiB together.  Steps must be finite and > 0, ranges finite and >= 0
+ * (the reference would loop forever or not at all). */
+typedef struct {
+    double range_x, range_y, range_theta;
+    double step_x, step_y, step_theta;
+    double score_usable_range_min, score_usable_range_max;
+} lgs_gs_params;
+
+/* The window values of one axis: the literal loop above, on the host (no
+ * context, no device).  Returns their count and writes the first
+ * min(count, cap) of them to out (out may be NULL when cap is 0); on bad
+ * arguments (step <= 0 or not finite, range negative or not finite, more than
+ * 4096 values) returns -LGS_ERR_INVALID_ARG: negative, so that a status can
+ * never be taken for a count.  The matcher calls the same loop. */
+int  lgs_gs_steps(double range, double step, double* out, int cap);
+/* OptimizePose(gridMap, scanData, initialPose, thr) (:44-114) for n scans
+ * against one map.  Summaries as the RTCSM ones with win = (nx, ny, nt) the
+ * window's value counts, best_win = the best pose's (ix, iy, it) or
+ * (-1, -1, -1) when nothing is found (cost, covariance and estimate are then
+ * evaluated at sp, as the reference does), steps = the three steps, score_max
+ * and score_threshold raw sums, coarse_blocks = poses scored, fine_blocks = 0. */
+int  lgs_gs_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
+                                const lgs_cost_ge_params* cost, const lgs_scan* const* scans,
+                                const lgs_pose2d* initial_poses, int n, double normalized_score_threshold,
+                                lgs_rtcsm_summary* out);
+/* OptimizePose(query) (:31-41): threshold DBL_MIN */
+int  lgs_gs_optimize_pose_query(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
+                                const lgs_cost_ge_params* cost, const lgs_scan* scan, lgs_pose2d initial_pose,
+                                lgs_rtcsm_summary* out);
+/* Diagnostics: every pose's score in (iy, ix, it) order (nx * ny * nt doubles;
+ * cap = the room in `scores`, LGS_ERR_INVALID_ARG when smaller). */
+int  lgs_gs_dense_scores(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params, const lgs_scan* scan,
+                         lgs_pose2d initial_pose, double* scores, long long cap);
+/* LoopDetectorGridSearch::Detect + FindCorrespondingPose
+ * (C/mapping/loop_detector_grid_search.cpp:26-106): every candidate matched
+ * against its query's local map with the score threshold (lgs_loop_query.coarse
+ * is ignored); lgs_loop_result.score is the best raw score.  One result per
+ * candidate, as lgs_loop_detect_bb. */
+int  lgs_loop_detect_gs(lgs_ctx* ctx, const lgs_gs_params* params, const lgs_cost_ge_params* cost,
                         double score_threshold, const lgs_loop_query* queries, int num_queries,
                         const lgs_loop_candidate* candidates, int num_candidates,
                         lgs_loop_result* results);

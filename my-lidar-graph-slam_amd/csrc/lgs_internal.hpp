@@ -87,6 +87,7 @@ enum Slot {
     S_KEEP,         // int: kept-superblock work list of a batch (k_keep / k_coarse_list)
     S_COLL,         // lgs_loop_records_allgather: send block + gathered rows (lgs_coll.hip)
     S_ZTILE,        // unsigned: zero-tile words of the per-map passes (k_rtcsm.hip ZeroTiles), per set
+    S_GS0, S_GS1,   // grid search (k_gs.hip): trig / index tables; partials, results, error word
     // bank 1 of the per-batch buffers: a batched call keeps two 64-query
     // chunks in flight (the next chunk's launches go out before the host
     // finishes the previous one), each in its own bank (lgs_ctx::banked)
@@ -248,6 +249,7 @@ enum KernelId { K_PROJECT = 0, K_COARSE, K_SEED, K_SELECT, K_FINE, K_REPLAY, K_C
                 K_LINSOLVE, K_RAY_EMIT, K_RAY_APPLY, K_SUPER, K_SUPER_PLANES, K_BB_SCORE, K_BB_EXPAND,
                 K_COARSE_AUX,   // k_keep + k_unsafe_list: the work-list passes around k_coarse_list
                 K_MATCH_SMALL,  // k_match_small: a small window's whole search (one coarse block per angle)
+                K_GS_SCORE,     // k_gs_score: the grid-search matcher's score + workgroup argmax pass
                 K_NUM_KERNELS };
 extern const char* const kKernelNames[K_NUM_KERNELS];
 struct PendingTiming {

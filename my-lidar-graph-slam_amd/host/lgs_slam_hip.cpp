@@ -253,6 +253,38 @@ std::vector<DeviceGridPtr> ScanMatcherBranchBoundHip::ComputeCoarserMaps(const D
     return out;
 }
 
+// ------------------------------------------------- ScanMatcherGridSearchHip
+ScanMatcherGridSearchHip::ScanMatcherGridSearchHip(DevicePtr dev, const ScorePixelAccurateParams& sf,
+                                                   const CostGreedyEndpointParams& c, double rangeX, double rangeY,
+                                                   double rangeTheta, double stepX, double stepY, double stepTheta)
+    : mDev(std::move(dev))
+{
+    // the reference's constructor only stores its arguments (:9-27); invalid
+    // values surface as LGS_ERR_INVALID_ARG from the first OptimizePose
+    mParams = { rangeX, rangeY, rangeTheta, stepX, stepY, stepTheta, sf.mUsableRangeMin, sf.mUsableRangeMax };
+    mCost = { c.mUsableRangeMin, c.mUsableRangeMax, c.mHitAndMissedDist, c.mOccupancyThreshold,
+              c.mKernelSize, c.mScalingFactor, c.mStandardDeviation };
+}
+
+ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const ScanMatchingQuery& q)
+{
+    mDev->Check(lgs_gs_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
+                                           q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
+                "lgs_gs_optimize_pose_query");
+    return summary_of(mLast);
+}
+
+ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const DeviceGrid& gridMap, const ScanDataPtr& scanData,
+                                                           const RobotPose2D<double>& initialPose, double thr) const
+{
+    const lgs_scan* s = scanData->Handle();
+    const lgs_pose2d p = to_c(initialPose);
+    mDev->Check(lgs_gs_optimize_pose_batch(mDev->Handle(), gridMap.Handle(), &mParams, &mCost, &s, &p, 1, thr,
+                                           &mLast),
+                "lgs_gs_optimize_pose_batch");
+    return summary_of(mLast);
+}
+
 // ------------------------------------------------ ScanMatcherLinearSolverHip
 ScanMatcherLinearSolverHip::ScanMatcherLinearSolverHip(DevicePtr dev, int numOfIterationsMax,
                                                        double convergenceThreshold, double usableRangeMin,
@@ -497,6 +529,49 @@ void LoopDetectorBranchBoundHip::Detect(std::vector<LoopDetectionQuery>& queries
                "lgs_loop_detect_bb");
     for (const auto& r : out) {
         if (!r.found) continue;   // only detected loops, in query -> node order (:61-84)
+        LoopDetectionResult o;
+        o.mRelativePose = from_c(r.relative_pose);
+        o.mStartNodePose = from_c(r.start_node_pose);
+        o.mStartNodeIdx = r.start_node_index;
+        o.mEndNodeIdx = r.end_node_index;
+        o.mEstimatedCovMat = cov_of(r.covariance);
+        results.push_back(o);
+    }
+}
+
+// ------------------------------------------------- LoopDetectorGridSearchHip
+LoopDetectorGridSearchHip::LoopDetectorGridSearchHip(std::shared_ptr<ScanMatcherGridSearchHip> m, double thr)
+    : mScanMatcher(std::move(m)), mScoreThreshold(thr)
+{
+    if (!(thr > 0.0 && thr <= 1.0))   // the reference asserts this (:20-21)
+        throw Error(LGS_ERR_INVALID_ARG, "LoopDetectorGridSearchHip: score threshold must be in (0, 1]");
+}
+
+void LoopDetectorGridSearchHip::Detect(std::vector<LoopDetectionQuery>& queries,
+                                       std::vector<LoopDetectionResult>& results)
+{
+    results.clear();
+    if (queries.empty()) return;
+    const DevicePtr& dev = mScanMatcher->Dev();
+    std::vector<lgs_loop_query> qs;
+    std::vector<lgs_loop_candidate> cs;
+    for (auto& q : queries) {
+        lgs_loop_query c{};
+        c.map = q.mLocalMap->Handle();
+        c.local_map_node_pose = to_c(q.mLocalMapNodePose);
+        c.local_map_node_index = q.mLocalMapNodeIndex;
+        c.first_candidate = (int)cs.size();
+        c.num_candidates = (int)q.mPoseGraphNodes.size();
+        qs.push_back(c);
+        for (const auto& n : q.mPoseGraphNodes)
+            cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
+    }
+    std::vector<lgs_loop_result> out(cs.size());
+    dev->Check(lgs_loop_detect_gs(dev->Handle(), &mScanMatcher->Params(), &mScanMatcher->Cost(), mScoreThreshold,
+                                  qs.data(), (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
+               "lgs_loop_detect_gs");
+    for (const auto& r : out) {
+        if (!r.found) continue;   // only detected loops, in query -> node order (:58-80)
         LoopDetectionResult o;
         o.mRelativePose = from_c(r.relative_pose);
         o.mStartNodePose = from_c(r.start_node_pose);

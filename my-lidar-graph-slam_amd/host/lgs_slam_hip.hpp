@@ -16,6 +16,10 @@
 //   LoopDetectorRealTimeCorrelative::Detect
 //     (C/mapping/loop_detector_real_time_correlative.cpp:26-125)
 //                                                           LoopDetectorRealTimeCorrelativeHip
+//   ScanMatcherGridSearch (H/mapping/scan_matcher_grid_search.hpp)
+//                                                           ScanMatcherGridSearchHip
+//   LoopDetectorGridSearch::Detect
+//     (C/mapping/loop_detector_grid_search.cpp:26-106)     LoopDetectorGridSearchHip
 //
 // Everything is a thin RAII layer over the C-ABI (include/lgs_hip.h); the
 // compute runs in HIP kernels on the GPU.  Value types are self-contained
@@ -251,6 +255,31 @@ private:
     mutable lgs_rtcsm_summary mLast{};
 };
 
+// ScanMatcherGridSearch (C/mapping/scan_matcher_grid_search.cpp:9-114): every
+// pose of the window scored on the device.
+class ScanMatcherGridSearchHip final : public ScanMatcher {
+public:
+    ScanMatcherGridSearchHip(DevicePtr dev, const ScorePixelAccurateParams& scoreFunc,
+                             const CostGreedyEndpointParams& costFunc, double rangeX, double rangeY,
+                             double rangeTheta, double stepX, double stepY, double stepTheta);
+    // OptimizePose(query): threshold DBL_MIN (:31-41)
+    ScanMatchingSummary OptimizePose(const ScanMatchingQuery& queryInfo) override;
+    // the const overload used by the loop detector (:44-114)
+    ScanMatchingSummary OptimizePose(const DeviceGrid& gridMap, const ScanDataPtr& scanData,
+                                     const RobotPose2D<double>& initialPose,
+                                     double normalizedScoreThreshold) const;
+    const lgs_rtcsm_summary& LastSummary() const { return mLast; }
+    const lgs_gs_params& Params() const { return mParams; }
+    const lgs_cost_ge_params& Cost() const { return mCost; }
+    const DevicePtr& Dev() const { return mDev; }
+
+private:
+    DevicePtr mDev;
+    lgs_gs_params mParams{};
+    lgs_cost_ge_params mCost{};
+    mutable lgs_rtcsm_summary mLast{};
+};
+
 // ScanMatcherLinearSolver (C/mapping/scan_matcher_linear_solver.cpp:38-148)
 // with CostSquareError(usableRangeMin, usableRangeMax).
 class ScanMatcherLinearSolverHip final : public ScanMatcher {
@@ -369,6 +398,19 @@ public:
 
 private:
     std::shared_ptr<ScanMatcherBranchBoundHip> mScanMatcher;
+    double mScoreThreshold;
+};
+
+// LoopDetectorGridSearch (C/mapping/loop_detector_grid_search.cpp:10-106):
+// every node matched against its query's local map, found ones appended in
+// query -> node order; one batched device call for all of them.
+class LoopDetectorGridSearchHip {
+public:
+    LoopDetectorGridSearchHip(std::shared_ptr<ScanMatcherGridSearchHip> scanMatcher, double scoreThreshold);
+    void Detect(std::vector<LoopDetectionQuery>& queries, std::vector<LoopDetectionResult>& results);
+
+private:
+    std::shared_ptr<ScanMatcherGridSearchHip> mScanMatcher;
     double mScoreThreshold;
 };
 

@@ -48,7 +48,7 @@ LGS_OPT_DEVICE_TIMING = 34   # correlative chunks' kernels timed on the device (
 LGS_OPT_LEAN_PROJECT = 35    # batched chunks: only superblock bases projected; consumers form their rows
 KERNEL_IDS = ["k_project", "k_coarse", "k_seed", "k_select", "k_fine", "k_replay", "k_cost", "k_precompute",
               "k_linsolve", "k_ray_emit", "k_ray_apply", "k_super", "k_super_planes", "k_bb_score",
-              "k_bb_expand", "k_coarse_aux", "k_match_small"]   # lgs_ctx_kernel_stats order
+              "k_bb_expand", "k_coarse_aux", "k_match_small", "k_gs_score"]   # lgs_ctx_kernel_stats order
 
 
 class Pose2D(C.Structure):
@@ -117,6 +117,14 @@ class BBParams(C.Structure):
     scanRangeMax) + ScorePixelAccurate (usableRangeMin/Max)."""
     _fields_ = [("node_height_max", C.c_int), ("range_x", C.c_double), ("range_y", C.c_double),
                 ("range_theta", C.c_double), ("scan_range_max", C.c_double),
+                ("score_usable_range_min", C.c_double), ("score_usable_range_max", C.c_double)]
+
+
+class GSParams(C.Structure):
+    """lgs_gs_params: ScanMatcherGridSearch ctor (rangeX/Y/Theta, stepX/Y/Theta)
+    + ScorePixelAccurate (usableRangeMin/Max)."""
+    _fields_ = [("range_x", C.c_double), ("range_y", C.c_double), ("range_theta", C.c_double),
+                ("step_x", C.c_double), ("step_y", C.c_double), ("step_theta", C.c_double),
                 ("score_usable_range_min", C.c_double), ("score_usable_range_max", C.c_double)]
 
 
@@ -248,6 +256,16 @@ _PROTOS = [
     ("lgs_loop_detect_bb", C.c_int, [_P, C.POINTER(BBParams), C.POINTER(CostGEParams), C.c_double,
                                      C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
                                      C.POINTER(LoopResult)]),
+    ("lgs_gs_steps", C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int]),
+    ("lgs_gs_optimize_pose_batch", C.c_int, [_P, _P, C.POINTER(GSParams), C.POINTER(CostGEParams), C.POINTER(_P),
+                                             C.POINTER(Pose2D), C.c_int, C.c_double, C.POINTER(RtcsmSummary)]),
+    ("lgs_gs_optimize_pose_query", C.c_int, [_P, _P, C.POINTER(GSParams), C.POINTER(CostGEParams), _P, Pose2D,
+                                             C.POINTER(RtcsmSummary)]),
+    ("lgs_gs_dense_scores", C.c_int, [_P, _P, C.POINTER(GSParams), _P, Pose2D, C.POINTER(C.c_double),
+                                      C.c_longlong]),
+    ("lgs_loop_detect_gs", C.c_int, [_P, C.POINTER(GSParams), C.POINTER(CostGEParams), C.c_double,
+                                     C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
+                                     C.POINTER(LoopResult)]),
     ("lgs_loop_detect_rtcsm", C.c_int, [_P, C.POINTER(RtcsmParams), C.POINTER(CostGEParams), C.c_double,
                                         C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
                                         C.POINTER(LoopResult)]),
@@ -295,6 +313,18 @@ def load(path: str = None) -> C.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def gs_steps(rng: float, step: float) -> np.ndarray:
+    """lgs_gs_steps: the window values of one grid-search axis (host only, no
+    device); raises LgsError on bad arguments."""
+    lib = load()
+    n = lib.lgs_gs_steps(float(rng), float(step), None, 0)
+    if n < 0:
+        raise LgsError(f"gs_steps: status {-n}")
+    out = np.zeros(n)
+    lib.lgs_gs_steps(float(rng), float(step), dptr(out) if n else None, n)
+    return out
 
 
 def dptr(a: np.ndarray):
@@ -563,6 +593,45 @@ class Context:
         out = (LoopResult * max(1, len(candidates)))()
         self.check(self.lib.lgs_loop_detect_bb(self.h, C.byref(params), C.byref(cost), float(thr), qs,
                                                len(queries), cs, len(candidates), out), "loop_detect_bb")
+        return out
+
+    # ---- exhaustive grid-search matcher ----
+    def gs_optimize_pose_batch(self, grid, params: "GSParams", cost: CostGEParams, scans, inits, thr: float):
+        n = len(scans)
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in inits])
+        out = (RtcsmSummary * max(1, n))()
+        self.check(self.lib.lgs_gs_optimize_pose_batch(self.h, grid.h, C.byref(params), C.byref(cost), sarr, poses,
+                                                       n, float(thr), out), "gs_optimize_pose_batch")
+        return list(out)[:n]
+
+    def gs_optimize_pose_query(self, grid, params: "GSParams", cost: CostGEParams, scan, init) -> RtcsmSummary:
+        out = RtcsmSummary()
+        self.check(self.lib.lgs_gs_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
+                                                       Pose2D(*init), C.byref(out)), "gs_optimize_pose_query")
+        return out
+
+    def gs_dense_scores(self, grid, params: "GSParams", scan, init) -> np.ndarray:
+        """every pose's score, [ny, nx, nt] (the reference's loop order)"""
+        nx, ny, nt = (len(gs_steps(r, s)) for r, s in ((params.range_x, params.step_x),
+                                                        (params.range_y, params.step_y),
+                                                        (params.range_theta, params.step_theta)))
+        out = np.zeros((ny, nx, nt))
+        self.check(self.lib.lgs_gs_dense_scores(self.h, grid.h, C.byref(params), scan.h, Pose2D(*init), dptr(out),
+                                                out.size), "gs_dense_scores")
+        return out
+
+    def loop_detect_gs(self, params: "GSParams", cost: CostGEParams, thr: float, queries, candidates):
+        """as loop_detect, with LoopDetectorGridSearch (the coarse entry of a query is ignored)"""
+        qs = (LoopQuery * max(1, len(queries)))()
+        for i, (m, c, pose, idx, first, cnt) in enumerate(queries):
+            qs[i] = LoopQuery(m.h, None, Pose2D(*pose), idx, first, cnt)
+        cs = (LoopCandidate * max(1, len(candidates)))()
+        for i, (s, pose, idx) in enumerate(candidates):
+            cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
+        out = (LoopResult * max(1, len(candidates)))()
+        self.check(self.lib.lgs_loop_detect_gs(self.h, C.byref(params), C.byref(cost), float(thr), qs,
+                                               len(queries), cs, len(candidates), out), "loop_detect_gs")
         return out
 
     # ---- Gauss-Newton refine (K4) ----
