@@ -18,6 +18,7 @@ oracle_ref:
 cpptest: host oracle
 	$(MAKE) -C tests/cpp
 	$(MAKE) -C tests/cpp_gs
+	$(MAKE) -C tests/cpp_hc
 
 clean:
 	$(MAKE) -C my-lidar-graph-slam_amd/csrc clean
@@ -26,5 +27,6 @@ clean:
 	$(MAKE) -C oracle/ref clean
 	$(MAKE) -C tests/cpp clean
 	$(MAKE) -C tests/cpp_gs clean
+	$(MAKE) -C tests/cpp_hc clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean

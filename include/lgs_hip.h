@@ -656,6 +656,72 @@ int  lgs_loop_detect_gs(lgs_ctx* ctx, const lgs_gs_params* params, const lgs_cos
                         const lgs_loop_candidate* candidates, int num_candidates,
                         lgs_loop_result* results);
 
+/* ---- hill-climbing matcher (ScanMatcherHillClimbing + CostGreedyEndpoint) ----
+ * Replaces ScanMatcherHillClimbing::OptimizePose
+ * (C/mapping/scan_matcher_hill_climbing.cpp:26-109), the matcher the launcher
+ * falls back to (C/slam_launcher.cpp:769-772).  The walk runs on the device,
+ * one workgroup per match, and every value of its ScanMatchingSummary equals
+ * the reference's bit for bit: the cost's exp() term takes one of at most
+ * (2K+1)^2 + 1 values (lgs_hc_term_table), which the host evaluates with libm
+ * and the device selects from.  Field order follows the
+ * constructor (linearStep, angularStep, maxIterations, maxNumOfRefinements).
+ * Caps (LGS_ERR_INVALID_ARG beyond them): steps finite and > 0, initial poses
+ * finite, max_iterations <= 65536 (values <= 1 run one pass, as the
+ * reference's do/while does), kernel_size in [0, 16], standard deviation and
+ * map resolution finite and > 0.  An angle outside the restated sincos domain
+ * (|theta + angle| >= 105414350) fails with LGS_ERR_INTERNAL. */
+typedef struct {
+    double linear_step, angular_step;
+    int max_iterations, max_num_of_refinements;
+} lgs_hc_params;
+
+typedef struct {
+    /* ScanMatchingSummary (H/mapping/scan_matcher.hpp:147-174) */
+    int pose_found;                 /* always 1 (:106-108) */
+    double normalized_cost;         /* minCost / NumOfScans() (:96) */
+    lgs_pose2d initial_pose, estimated_pose;   /* MoveBackward(bestPose, relPose) (:98-99) */
+    double covariance[9];           /* CostGreedyEndpoint::ComputeCovariance at bestPose, row-major */
+    /* diagnostics */
+    lgs_pose2d best_sensor_pose;
+    double min_cost;
+    double final_linear_step, final_angular_step;
+    int num_iterations;             /* the reference's variables at exit (:48-50) */
+    int num_refinements;
+    int passes;                     /* bodies of the do/while run */
+    int cost_evals;                 /* 1 + 6 per pass + 6 for the gradient */
+} lgs_hc_summary;
+
+/* The values the cost's exp() term can take (no context, no device): entry
+ * q = (ky + K) * (2K+1) + (kx + K) holds GridMap::SquaredDistance of the kernel
+ * offset (H/grid_map/grid_map.hpp:894-902: dX = kx * res, dY = ky * res,
+ * sq = dX * dX + dY * dY), entry (2K+1)^2 the start value with dX = dY =
+ * (K+1) * res (C/mapping/cost_function_greedy_endpoint.cpp:66-67), and
+ * term = exp(-0.5 * sq / variance) with libm's exp (:101), variance =
+ * standard_deviation^2.  Returns the entry count and writes the first
+ * min(count, cap) entries (sq and term may be NULL when cap is 0); on bad
+ * arguments returns -LGS_ERR_INVALID_ARG. */
+int  lgs_hc_term_table(const lgs_cost_ge_params* cost, double res, double* sq, double* term, int cap);
+/* OptimizePose(query) (:26-109) */
+int  lgs_hc_optimize_pose_query(lgs_ctx* ctx, const lgs_grid* grid, const lgs_hc_params* params,
+                                const lgs_cost_ge_params* cost, const lgs_scan* scan, lgs_pose2d initial_pose,
+                                lgs_hc_summary* out);
+/* n scans and poses, one grid per item; pointers may repeat.  One launch per
+ * chunk (4096 matches of one map resolution).  Equal to n lone calls. */
+int  lgs_hc_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_hc_params* params,
+                                const lgs_cost_ge_params* cost, const lgs_scan* const* scans,
+                                const lgs_pose2d* initial_poses, int n, lgs_hc_summary* out);
+/* Diagnostics: the walk's per-pass (accepted move index 0..5 in the order of
+ * :30-32, or -1; minCost after the pass) of one match.  Returns the pass count
+ * and writes the first min(count, cap) passes; a failure returns the negated
+ * status. */
+int  lgs_hc_trace(lgs_ctx* ctx, const lgs_grid* grid, const lgs_hc_params* params, const lgs_cost_ge_params* cost,
+                  const lgs_scan* scan, lgs_pose2d initial_pose, int* moves, double* costs, int cap);
+/* CostGreedyEndpoint::Cost (:32-111) at n sensor poses of one scan, equal to
+ * the reference's bit for bit: the matcher's cost code on its own
+ * (lgs_cost_greedy_endpoint keeps its 1e-5 contract). */
+int  lgs_cost_ge_exact(lgs_ctx* ctx, const lgs_grid* grid, const lgs_cost_ge_params* cost, const lgs_scan* scan,
+                       const lgs_pose2d* poses, int n, double* out);
+
 /* ---- K4: Gauss-Newton refine (ScanMatcherLinearSolver + CostSquareError) ----
  * Replaces ScanMatcherLinearSolver::OptimizePose (C/mapping/scan_matcher_linear_solver.cpp:38-85,
  * H/mapping/scan_matcher_linear_solver.hpp:15-56) with its CostSquareError

@@ -285,6 +285,33 @@ ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const DeviceGrid& gri
     return summary_of(mLast);
 }
 
+// ----------------------------------------------- ScanMatcherHillClimbingHip
+ScanMatcherHillClimbingHip::ScanMatcherHillClimbingHip(DevicePtr dev, double linearStep, double angularStep,
+                                                       int maxIterations, int maxNumOfRefinements,
+                                                       const CostGreedyEndpointParams& c)
+    : mDev(std::move(dev))
+{
+    // the reference's constructor only stores its arguments (:10-23); invalid
+    // values surface as LGS_ERR_INVALID_ARG from the first OptimizePose
+    mParams = { linearStep, angularStep, maxIterations, maxNumOfRefinements };
+    mCost = { c.mUsableRangeMin, c.mUsableRangeMax, c.mHitAndMissedDist, c.mOccupancyThreshold,
+              c.mKernelSize, c.mScalingFactor, c.mStandardDeviation };
+}
+
+ScanMatchingSummary ScanMatcherHillClimbingHip::OptimizePose(const ScanMatchingQuery& q)
+{
+    mDev->Check(lgs_hc_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
+                                           q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
+                "lgs_hc_optimize_pose_query");
+    ScanMatchingSummary o;
+    o.mPoseFound = mLast.pose_found != 0;
+    o.mNormalizedCost = mLast.normalized_cost;
+    o.mInitialPose = from_c(mLast.initial_pose);
+    o.mEstimatedPose = from_c(mLast.estimated_pose);
+    o.mEstimatedCovariance = cov_of(mLast.covariance);
+    return o;
+}
+
 // ------------------------------------------------ ScanMatcherLinearSolverHip
 ScanMatcherLinearSolverHip::ScanMatcherLinearSolverHip(DevicePtr dev, int numOfIterationsMax,
                                                        double convergenceThreshold, double usableRangeMin,

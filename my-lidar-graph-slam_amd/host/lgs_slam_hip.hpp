@@ -20,6 +20,8 @@
 //                                                           ScanMatcherGridSearchHip
 //   LoopDetectorGridSearch::Detect
 //     (C/mapping/loop_detector_grid_search.cpp:26-106)     LoopDetectorGridSearchHip
+//   ScanMatcherHillClimbing (H/mapping/scan_matcher_hill_climbing.hpp)
+//                                                           ScanMatcherHillClimbingHip
 //
 // Everything is a thin RAII layer over the C-ABI (include/lgs_hip.h); the
 // compute runs in HIP kernels on the GPU.  Value types are self-contained
@@ -278,6 +280,28 @@ private:
     lgs_gs_params mParams{};
     lgs_cost_ge_params mCost{};
     mutable lgs_rtcsm_summary mLast{};
+};
+
+// ScanMatcherHillClimbing (C/mapping/scan_matcher_hill_climbing.cpp:10-109),
+// the launcher's fall-back matcher: the whole walk on the device, its summary
+// equal to the reference's bit for bit.  Argument order as
+// the reference's constructor, the cost function last.
+class ScanMatcherHillClimbingHip final : public ScanMatcher {
+public:
+    ScanMatcherHillClimbingHip(DevicePtr dev, double linearStep, double angularStep, int maxIterations,
+                               int maxNumOfRefinements, const CostGreedyEndpointParams& costFunc);
+    ScanMatchingSummary OptimizePose(const ScanMatchingQuery& queryInfo) override;
+    // full device summary of the last OptimizePose (best sensor pose, counters, final steps)
+    const lgs_hc_summary& LastSummary() const { return mLast; }
+    const lgs_hc_params& Params() const { return mParams; }
+    const lgs_cost_ge_params& Cost() const { return mCost; }
+    const DevicePtr& Dev() const { return mDev; }
+
+private:
+    DevicePtr mDev;
+    lgs_hc_params mParams{};
+    lgs_cost_ge_params mCost{};
+    lgs_hc_summary mLast{};
 };
 
 // ScanMatcherLinearSolver (C/mapping/scan_matcher_linear_solver.cpp:38-148)

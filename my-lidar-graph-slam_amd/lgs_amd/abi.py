@@ -128,6 +128,22 @@ class GSParams(C.Structure):
                 ("score_usable_range_min", C.c_double), ("score_usable_range_max", C.c_double)]
 
 
+class HCParams(C.Structure):
+    """lgs_hc_params: ScanMatcherHillClimbing ctor (linearStep, angularStep,
+    maxIterations, maxNumOfRefinements)."""
+    _fields_ = [("linear_step", C.c_double), ("angular_step", C.c_double), ("max_iterations", C.c_int),
+                ("max_num_of_refinements", C.c_int)]
+
+
+class HCSummary(C.Structure):
+    """lgs_hc_summary: ScanMatchingSummary, then the walk's diagnostics."""
+    _fields_ = [("pose_found", C.c_int), ("normalized_cost", C.c_double), ("initial_pose", Pose2D),
+                ("estimated_pose", Pose2D), ("covariance", C.c_double * 9), ("best_sensor_pose", Pose2D),
+                ("min_cost", C.c_double), ("final_linear_step", C.c_double), ("final_angular_step", C.c_double),
+                ("num_iterations", C.c_int), ("num_refinements", C.c_int), ("passes", C.c_int),
+                ("cost_evals", C.c_int)]
+
+
 class BuilderParams(C.Structure):
     _fields_ = [("usable_range_min", C.c_double), ("usable_range_max", C.c_double),
                 ("prob_hit", C.c_double), ("prob_miss", C.c_double)]
@@ -266,6 +282,16 @@ _PROTOS = [
     ("lgs_loop_detect_gs", C.c_int, [_P, C.POINTER(GSParams), C.POINTER(CostGEParams), C.c_double,
                                      C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
                                      C.POINTER(LoopResult)]),
+    ("lgs_hc_term_table", C.c_int, [C.POINTER(CostGEParams), C.c_double, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.c_int]),
+    ("lgs_hc_optimize_pose_query", C.c_int, [_P, _P, C.POINTER(HCParams), C.POINTER(CostGEParams), _P, Pose2D,
+                                             C.POINTER(HCSummary)]),
+    ("lgs_hc_optimize_pose_batch", C.c_int, [_P, C.POINTER(_P), C.POINTER(HCParams), C.POINTER(CostGEParams),
+                                             C.POINTER(_P), C.POINTER(Pose2D), C.c_int, C.POINTER(HCSummary)]),
+    ("lgs_hc_trace", C.c_int, [_P, _P, C.POINTER(HCParams), C.POINTER(CostGEParams), _P, Pose2D,
+                               C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]),
+    ("lgs_cost_ge_exact", C.c_int, [_P, _P, C.POINTER(CostGEParams), _P, C.POINTER(Pose2D), C.c_int,
+                                    C.POINTER(C.c_double)]),
     ("lgs_loop_detect_rtcsm", C.c_int, [_P, C.POINTER(RtcsmParams), C.POINTER(CostGEParams), C.c_double,
                                         C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
                                         C.POINTER(LoopResult)]),
@@ -325,6 +351,19 @@ def gs_steps(rng: float, step: float) -> np.ndarray:
     out = np.zeros(n)
     lib.lgs_gs_steps(float(rng), float(step), dptr(out) if n else None, n)
     return out
+
+
+def hc_term_table(cost: "CostGEParams", res: float):
+    """lgs_hc_term_table: (sq, term), the squared distances of the kernel
+    offsets and of the start offset and exp(-0.5 * sq / variance) of each
+    (host only, no device); raises LgsError on bad arguments."""
+    lib = load()
+    n = lib.lgs_hc_term_table(C.byref(cost), float(res), None, None, 0)
+    if n < 0:
+        raise LgsError(f"hc_term_table: status {-n}")
+    sq, term = np.zeros(n), np.zeros(n)
+    lib.lgs_hc_term_table(C.byref(cost), float(res), dptr(sq), dptr(term), n)
+    return sq, term
 
 
 def dptr(a: np.ndarray):
@@ -633,6 +672,47 @@ class Context:
         self.check(self.lib.lgs_loop_detect_gs(self.h, C.byref(params), C.byref(cost), float(thr), qs,
                                                len(queries), cs, len(candidates), out), "loop_detect_gs")
         return out
+
+    # ---- hill-climbing matcher ----
+    def hc_optimize_pose_query(self, grid, params: "HCParams", cost: CostGEParams, scan, init) -> "HCSummary":
+        out = HCSummary()
+        self.check(self.lib.lgs_hc_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
+                                                       Pose2D(*init), C.byref(out)), "hc_optimize_pose_query")
+        return out
+
+    def hc_optimize_pose_batch(self, grids, params: "HCParams", cost: CostGEParams, scans, inits):
+        """n independent matches, one launch per chunk; grids: one map per
+        match (or a single map for all)"""
+        n = len(scans)
+        if not isinstance(grids, (list, tuple)):
+            grids = [grids] * n
+        garr = (_P * max(1, n))(*[g.h for g in grids])
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in inits])
+        out = (HCSummary * max(1, n))()
+        self.check(self.lib.lgs_hc_optimize_pose_batch(self.h, garr, C.byref(params), C.byref(cost), sarr, poses, n,
+                                                       out), "hc_optimize_pose_batch")
+        return list(out)[:n]
+
+    def hc_trace(self, grid, params: "HCParams", cost: CostGEParams, scan, init):
+        """(moves, costs): the accepted move (or -1) and minCost of every pass"""
+        cap = max(1, params.max_iterations)
+        moves = np.zeros(cap, dtype=np.int32)
+        costs = np.zeros(cap)
+        n = self.lib.lgs_hc_trace(self.h, grid.h, C.byref(params), C.byref(cost), scan.h, Pose2D(*init),
+                                  moves.ctypes.data_as(C.POINTER(C.c_int)), dptr(costs), cap)
+        if n < 0:
+            self.check(-n, "hc_trace")
+        return moves[:n].copy(), costs[:n].copy()
+
+    def cost_ge_exact(self, grid, cost: CostGEParams, scan, poses) -> np.ndarray:
+        """the greedy-endpoint cost at every sensor pose, bit-exact"""
+        n = len(poses)
+        parr = (Pose2D * max(1, n))(*[Pose2D(*p) for p in poses])
+        out = np.zeros(max(1, n))
+        self.check(self.lib.lgs_cost_ge_exact(self.h, grid.h, C.byref(cost), scan.h, parr, n, dptr(out)),
+                   "cost_ge_exact")
+        return out[:n]
 
     # ---- Gauss-Newton refine (K4) ----
     def linsolve(self, grid, params: LinsolveParams, scan, init, trajectory: bool = False):
