@@ -19,6 +19,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp
 	$(MAKE) -C tests/cpp_gs
 	$(MAKE) -C tests/cpp_hc
+	$(MAKE) -C tests/cpp_hc_sq
 
 clean:
 	$(MAKE) -C my-lidar-graph-slam_amd/csrc clean
@@ -28,5 +29,6 @@ clean:
 	$(MAKE) -C tests/cpp clean
 	$(MAKE) -C tests/cpp_gs clean
 	$(MAKE) -C tests/cpp_hc clean
+	$(MAKE) -C tests/cpp_hc_sq clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean

@@ -49,6 +49,11 @@
  *                                C/mapping/scan_matcher_linear_solver.cpp:38-148
  *   lgs_cost_square_error        CostSquareError::Cost / ComputeCovariance
  *                                C/mapping/cost_function_square_error.cpp:21-58, :112-135
+ *   lgs_cost_square_error_batch  the same at n (map, scan, sensor pose) items in one launch
+ *   lgs_summaries_apply_cost_sq  what the correlative, branch-and-bound and grid-search matchers
+ *                                return when constructed with CostSquareError
+ *   lgs_hc_sq_optimize_pose_query ScanMatcherHillClimbing::OptimizePose(query) with CostSquareError
+ *                                C/mapping/scan_matcher_hill_climbing.cpp:26-109
  *   lgs_grid_precompute_pyramid  PrecomputeGridMaps C/mapping/grid_map_builder.cpp:471-495
  *   lgs_bb_optimize_pose_batch   ScanMatcherBranchBound::OptimizePose(map, pyramid, scan, pose, thr)
  *                                C/mapping/scan_matcher_branch_bound.cpp:47-154
@@ -765,6 +770,54 @@ int  lgs_linsolve_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid,
 int  lgs_cost_square_error(lgs_ctx* ctx, const lgs_grid* grid, double usable_range_min,
                            double usable_range_max, const lgs_scan* scan, lgs_pose2d sensor_pose,
                            double* out_cost, double* out_covariance);
+
+/* ---- CostSquareError for every scan matcher ----
+ * The reference builds each matcher's cost through CreateCostFunction
+ * (C/slam_launcher.cpp:96-107): "GreedyEndpoint" or "SquareError".  The entry
+ * points above take the greedy-endpoint cost; these give a matcher constructed
+ * with CostSquareError.  Every value equals the reference's
+ * bit for bit (the arithmetic of lgs_cost_square_error).  A square-error term
+ * needs no per-resolution table, so one call, and one launch, may mix maps of
+ * different size and resolution.
+ * Caps (LGS_ERR_INVALID_ARG beyond them): usable ranges, poses and map
+ * resolutions finite (resolution > 0), maps of fewer than 2^30 cells, scans
+ * of at least one beam.  An angle outside the restated sincos domain
+ * (|theta + angle| >= 105414350) fails with LGS_ERR_INTERNAL. */
+
+/* CostSquareError(usableRangeMin, usableRangeMax), cost_function_square_error.cpp:10-17 */
+typedef struct { double usable_range_min, usable_range_max; } lgs_cost_sq_params;
+
+/* Cost (:21-58) and, if out_covariance != NULL, ComputeCovariance (:112-135) of item j at
+ * sensor_poses[j] on grids[j] with scans[j]; pointers may repeat, grids may differ in size
+ * and resolution.  One launch per chunk (4096 items), one synchronisation per call.  Equal
+ * to n calls of lgs_cost_square_error byte for byte. */
+int  lgs_cost_square_error_batch(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_sq_params* cost,
+                                 const lgs_scan* const* scans, const lgs_pose2d* sensor_poses, int n,
+                                 double* out_cost /* n */, double* out_covariance /* 9 n or NULL */);
+
+/* What a matcher constructed with CostSquareError returns: summaries[j].normalized_cost =
+ * Cost(best_sensor_pose) / NumOfScans() and .covariance = ComputeCovariance(best_sensor_pose);
+ * every other field is left as it is.  For the summaries of the rtcsm, bb and gs entry points,
+ * which evaluate the cost after the search, at best_sensor_pose, whether or not a pose was found
+ * (scan_matcher_real_time_correlative.cpp:128-138, scan_matcher_grid_search.cpp:97-107). */
+int  lgs_summaries_apply_cost_sq(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_sq_params* cost,
+                                 const lgs_scan* const* scans, lgs_rtcsm_summary* summaries, int n);
+
+/* ScanMatcherHillClimbing with CostSquareError: the contracts, caps and status
+ * codes of the lgs_hc_* trio (kernel size and standard deviation apart), plus
+ * finite usable ranges.  lgs_hc_summary is reused with two differences:
+ * covariance is CostSquareError::ComputeCovariance at bestPose (the analytic
+ * gradient g, g g^T, + 0.01 on the diagonal), and cost_evals counts Cost calls
+ * only, 1 + 6 per pass: the square-error covariance calls Cost not once.
+ * lgs_hc_sq_trace returns the pass count, or the negated status. */
+int  lgs_hc_sq_optimize_pose_query(lgs_ctx* ctx, const lgs_grid* grid, const lgs_hc_params* params,
+                                   const lgs_cost_sq_params* cost, const lgs_scan* scan, lgs_pose2d initial_pose,
+                                   lgs_hc_summary* out);
+int  lgs_hc_sq_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_hc_params* params,
+                                   const lgs_cost_sq_params* cost, const lgs_scan* const* scans,
+                                   const lgs_pose2d* initial_poses, int n, lgs_hc_summary* out);
+int  lgs_hc_sq_trace(lgs_ctx* ctx, const lgs_grid* grid, const lgs_hc_params* params, const lgs_cost_sq_params* cost,
+                     const lgs_scan* scan, lgs_pose2d initial_pose, int* moves, double* costs, int cap);
 
 #ifdef __cplusplus
 }

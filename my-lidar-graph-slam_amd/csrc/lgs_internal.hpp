@@ -88,7 +88,7 @@ enum Slot {
     S_COLL,         // lgs_loop_records_allgather: send block + gathered rows (lgs_coll.hip)
     S_ZTILE,        // unsigned: zero-tile words of the per-map passes (k_rtcsm.hip ZeroTiles), per set
     S_GS0, S_GS1,   // grid search (k_gs.hip): trig / index tables; partials, results, error word
-    S_HC0, S_HC1,   // hill climbing (k_hc.hip): global term rows; records, trace, error word
+    S_HC0, S_HC1,   // hill climbing (k_hc.hip, k_hc_sq.hip): global term rows; records, trace, error word
     // bank 1 of the per-batch buffers: a batched call keeps two 64-query
     // chunks in flight (the next chunk's launches go out before the host
     // finishes the previous one), each in its own bank (lgs_ctx::banked)

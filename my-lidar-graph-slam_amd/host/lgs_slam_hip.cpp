@@ -158,6 +158,22 @@ CostGreedyEndpointParams CostGreedyEndpointParams::FromLauncherJson(double usabl
     return p;
 }
 
+static lgs_cost_ge_params ge_of(const CostGreedyEndpointParams& c)
+{
+    return { c.mUsableRangeMin, c.mUsableRangeMax, c.mHitAndMissedDist, c.mOccupancyThreshold,
+             c.mKernelSize, c.mScalingFactor, c.mStandardDeviation };
+}
+
+// a search matcher constructed with CostSquareError: Cost / NumOfScans() and
+// ComputeCovariance at the best sensor pose replace the search entry point's
+static void apply_cost_sq(const DevicePtr& dev, const lgs_cost_sq_params* cost, const lgs_grid* grid,
+                          const lgs_scan* scan, lgs_rtcsm_summary* summary)
+{
+    if (!cost) return;
+    dev->Check(lgs_summaries_apply_cost_sq(dev->Handle(), &grid, cost, &scan, summary, 1),
+               "lgs_summaries_apply_cost_sq");
+}
+
 // ------------------------------------------ ScanMatcherRealTimeCorrelativeHip
 ScanMatcherRealTimeCorrelativeHip::ScanMatcherRealTimeCorrelativeHip(DevicePtr dev,
                                                                      const CostGreedyEndpointParams& c,
@@ -169,8 +185,18 @@ ScanMatcherRealTimeCorrelativeHip::ScanMatcherRealTimeCorrelativeHip(DevicePtr d
     // the reference's constructor only stores its arguments (:13-27); invalid
     // values surface as LGS_ERR_INVALID_ARG from the first OptimizePose
     mParams = { lowResolution, rangeX, rangeY, rangeTheta, scanRangeMax };
-    mCost = { c.mUsableRangeMin, c.mUsableRangeMax, c.mHitAndMissedDist, c.mOccupancyThreshold,
-              c.mKernelSize, c.mScalingFactor, c.mStandardDeviation };
+    mCost = ge_of(c);
+}
+
+ScanMatcherRealTimeCorrelativeHip::ScanMatcherRealTimeCorrelativeHip(DevicePtr dev, const CostSquareErrorParams& c,
+                                                                     int lowResolution, double rangeX,
+                                                                     double rangeY, double rangeTheta,
+                                                                     double scanRangeMax)
+    : ScanMatcherRealTimeCorrelativeHip(std::move(dev), CostGreedyEndpointParams(), lowResolution, rangeX, rangeY,
+                                        rangeTheta, scanRangeMax)
+{
+    mCostSq = { c.mUsableRangeMin, c.mUsableRangeMax };
+    mSquareError = true;
 }
 
 ScanMatchingSummary ScanMatcherRealTimeCorrelativeHip::OptimizePose(const ScanMatchingQuery& q)
@@ -178,6 +204,7 @@ ScanMatchingSummary ScanMatcherRealTimeCorrelativeHip::OptimizePose(const ScanMa
     mDev->Check(lgs_rtcsm_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
                                               q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                 "lgs_rtcsm_optimize_pose_query");
+    apply_cost_sq(mDev, CostSquareError(), q.mGridMap->Handle(), q.mScanData->Handle(), &mLast);
     return summary_of(mLast);
 }
 
@@ -190,6 +217,7 @@ ScanMatchingSummary ScanMatcherRealTimeCorrelativeHip::OptimizePose(const Device
     mDev->Check(lgs_rtcsm_optimize_pose(mDev->Handle(), gridMap.Handle(), precompMap.Handle(), &mParams, &mCost,
                                         scanData->Handle(), to_c(initialPose), thr, &mLast),
                 "lgs_rtcsm_optimize_pose");
+    apply_cost_sq(mDev, CostSquareError(), gridMap.Handle(), scanData->Handle(), &mLast);
     return summary_of(mLast);
 }
 
@@ -210,8 +238,18 @@ ScanMatcherBranchBoundHip::ScanMatcherBranchBoundHip(DevicePtr dev, const ScoreP
     : mDev(std::move(dev))
 {
     mParams = { nodeHeightMax, rangeX, rangeY, rangeTheta, scanRangeMax, sf.mUsableRangeMin, sf.mUsableRangeMax };
-    mCost = { c.mUsableRangeMin, c.mUsableRangeMax, c.mHitAndMissedDist, c.mOccupancyThreshold,
-              c.mKernelSize, c.mScalingFactor, c.mStandardDeviation };
+    mCost = ge_of(c);
+}
+
+ScanMatcherBranchBoundHip::ScanMatcherBranchBoundHip(DevicePtr dev, const ScorePixelAccurateParams& sf,
+                                                     const CostSquareErrorParams& c, int nodeHeightMax,
+                                                     double rangeX, double rangeY, double rangeTheta,
+                                                     double scanRangeMax)
+    : ScanMatcherBranchBoundHip(std::move(dev), sf, CostGreedyEndpointParams(), nodeHeightMax, rangeX, rangeY,
+                                rangeTheta, scanRangeMax)
+{
+    mCostSq = { c.mUsableRangeMin, c.mUsableRangeMax };
+    mSquareError = true;
 }
 
 ScanMatchingSummary ScanMatcherBranchBoundHip::OptimizePose(const ScanMatchingQuery& q)
@@ -219,6 +257,7 @@ ScanMatchingSummary ScanMatcherBranchBoundHip::OptimizePose(const ScanMatchingQu
     mDev->Check(lgs_bb_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
                                            q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                 "lgs_bb_optimize_pose_query");
+    apply_cost_sq(mDev, CostSquareError(), q.mGridMap->Handle(), q.mScanData->Handle(), &mLast);
     return summary_of(mLast);
 }
 
@@ -236,6 +275,7 @@ ScanMatchingSummary ScanMatcherBranchBoundHip::OptimizePose(const DeviceGrid& gr
     mDev->Check(lgs_bb_optimize_pose_batch(mDev->Handle(), gridMap.Handle(), pyr.data(), &mParams, &mCost, &s, &p,
                                            1, thr, &mLast),
                 "lgs_bb_optimize_pose_batch");
+    apply_cost_sq(mDev, CostSquareError(), gridMap.Handle(), s, &mLast);
     return summary_of(mLast);
 }
 
@@ -262,8 +302,17 @@ ScanMatcherGridSearchHip::ScanMatcherGridSearchHip(DevicePtr dev, const ScorePix
     // the reference's constructor only stores its arguments (:9-27); invalid
     // values surface as LGS_ERR_INVALID_ARG from the first OptimizePose
     mParams = { rangeX, rangeY, rangeTheta, stepX, stepY, stepTheta, sf.mUsableRangeMin, sf.mUsableRangeMax };
-    mCost = { c.mUsableRangeMin, c.mUsableRangeMax, c.mHitAndMissedDist, c.mOccupancyThreshold,
-              c.mKernelSize, c.mScalingFactor, c.mStandardDeviation };
+    mCost = ge_of(c);
+}
+
+ScanMatcherGridSearchHip::ScanMatcherGridSearchHip(DevicePtr dev, const ScorePixelAccurateParams& sf,
+                                                   const CostSquareErrorParams& c, double rangeX, double rangeY,
+                                                   double rangeTheta, double stepX, double stepY, double stepTheta)
+    : ScanMatcherGridSearchHip(std::move(dev), sf, CostGreedyEndpointParams(), rangeX, rangeY, rangeTheta, stepX,
+                               stepY, stepTheta)
+{
+    mCostSq = { c.mUsableRangeMin, c.mUsableRangeMax };
+    mSquareError = true;
 }
 
 ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const ScanMatchingQuery& q)
@@ -271,6 +320,7 @@ ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const ScanMatchingQue
     mDev->Check(lgs_gs_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
                                            q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                 "lgs_gs_optimize_pose_query");
+    apply_cost_sq(mDev, CostSquareError(), q.mGridMap->Handle(), q.mScanData->Handle(), &mLast);
     return summary_of(mLast);
 }
 
@@ -282,6 +332,7 @@ ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const DeviceGrid& gri
     mDev->Check(lgs_gs_optimize_pose_batch(mDev->Handle(), gridMap.Handle(), &mParams, &mCost, &s, &p, 1, thr,
                                            &mLast),
                 "lgs_gs_optimize_pose_batch");
+    apply_cost_sq(mDev, CostSquareError(), gridMap.Handle(), s, &mLast);
     return summary_of(mLast);
 }
 
@@ -294,15 +345,29 @@ ScanMatcherHillClimbingHip::ScanMatcherHillClimbingHip(DevicePtr dev, double lin
     // the reference's constructor only stores its arguments (:10-23); invalid
     // values surface as LGS_ERR_INVALID_ARG from the first OptimizePose
     mParams = { linearStep, angularStep, maxIterations, maxNumOfRefinements };
-    mCost = { c.mUsableRangeMin, c.mUsableRangeMax, c.mHitAndMissedDist, c.mOccupancyThreshold,
-              c.mKernelSize, c.mScalingFactor, c.mStandardDeviation };
+    mCost = ge_of(c);
+}
+
+ScanMatcherHillClimbingHip::ScanMatcherHillClimbingHip(DevicePtr dev, double linearStep, double angularStep,
+                                                       int maxIterations, int maxNumOfRefinements,
+                                                       const CostSquareErrorParams& c)
+    : ScanMatcherHillClimbingHip(std::move(dev), linearStep, angularStep, maxIterations, maxNumOfRefinements,
+                                 CostGreedyEndpointParams())
+{
+    mCostSq = { c.mUsableRangeMin, c.mUsableRangeMax };
+    mSquareError = true;
 }
 
 ScanMatchingSummary ScanMatcherHillClimbingHip::OptimizePose(const ScanMatchingQuery& q)
 {
-    mDev->Check(lgs_hc_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
-                                           q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
-                "lgs_hc_optimize_pose_query");
+    if (mSquareError)
+        mDev->Check(lgs_hc_sq_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCostSq,
+                                                  q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
+                    "lgs_hc_sq_optimize_pose_query");
+    else
+        mDev->Check(lgs_hc_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
+                                               q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
+                    "lgs_hc_optimize_pose_query");
     ScanMatchingSummary o;
     o.mPoseFound = mLast.pose_found != 0;
     o.mNormalizedCost = mLast.normalized_cost;

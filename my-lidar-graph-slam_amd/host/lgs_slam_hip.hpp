@@ -197,10 +197,27 @@ struct CostGreedyEndpointParams {
                                                      double jsonScale);
 };
 
+// CostSquareError (C/mapping/cost_function_square_error.cpp:10-17).  The
+// launcher's CreateCostFunction (C/slam_launcher.cpp:96-107) gives a matcher
+// either cost; every matcher below has a constructor for each.  A search
+// matcher (correlative, branch-and-bound, grid search) constructed with this
+// one runs its search as ever and then evaluates Cost and ComputeCovariance
+// of this cost at the best sensor pose, as the reference does
+// (lgs_summaries_apply_cost_sq); the search entry point's own
+// greedy-endpoint cost, evaluated with the default parameters, is overwritten.
+// The loop detectors read only Params() and Cost() of their matcher: they
+// stay greedy-endpoint.
+struct CostSquareErrorParams {
+    double mUsableRangeMin = 0.01, mUsableRangeMax = 20.0;
+};
+
 // ScanMatcherRealTimeCorrelative (C/mapping/scan_matcher_real_time_correlative.cpp:14-256)
 class ScanMatcherRealTimeCorrelativeHip final : public ScanMatcher {
 public:
     ScanMatcherRealTimeCorrelativeHip(DevicePtr dev, const CostGreedyEndpointParams& costFunc,
+                                      int lowResolution, double rangeX, double rangeY, double rangeTheta,
+                                      double scanRangeMax);
+    ScanMatcherRealTimeCorrelativeHip(DevicePtr dev, const CostSquareErrorParams& costFunc,
                                       int lowResolution, double rangeX, double rangeY, double rangeTheta,
                                       double scanRangeMax);
     // OptimizePose(query): coarse map + search with threshold DBL_MIN (:31-47)
@@ -215,12 +232,16 @@ public:
     const lgs_rtcsm_summary& LastSummary() const { return mLast; }
     const lgs_rtcsm_params& Params() const { return mParams; }
     const lgs_cost_ge_params& Cost() const { return mCost; }
+    // the square-error cost of a matcher constructed with one, else null
+    const lgs_cost_sq_params* CostSquareError() const { return mSquareError ? &mCostSq : nullptr; }
     const DevicePtr& Dev() const { return mDev; }
 
 private:
     DevicePtr mDev;
     lgs_rtcsm_params mParams{};
     lgs_cost_ge_params mCost{};
+    lgs_cost_sq_params mCostSq{};
+    bool mSquareError = false;
     mutable lgs_rtcsm_summary mLast{};
 };
 
@@ -237,6 +258,9 @@ public:
     ScanMatcherBranchBoundHip(DevicePtr dev, const ScorePixelAccurateParams& scoreFunc,
                               const CostGreedyEndpointParams& costFunc, int nodeHeightMax, double rangeX,
                               double rangeY, double rangeTheta, double scanRangeMax);
+    ScanMatcherBranchBoundHip(DevicePtr dev, const ScorePixelAccurateParams& scoreFunc,
+                              const CostSquareErrorParams& costFunc, int nodeHeightMax, double rangeX,
+                              double rangeY, double rangeTheta, double scanRangeMax);
     // OptimizePose(query): pyramid + search with threshold DBL_MIN (:29-44)
     ScanMatchingSummary OptimizePose(const ScanMatchingQuery& queryInfo) override;
     // the const overload used by the loop detector (:47-154)
@@ -248,12 +272,16 @@ public:
     const lgs_rtcsm_summary& LastSummary() const { return mLast; }
     const lgs_bb_params& Params() const { return mParams; }
     const lgs_cost_ge_params& Cost() const { return mCost; }
+    // the square-error cost of a matcher constructed with one, else null
+    const lgs_cost_sq_params* CostSquareError() const { return mSquareError ? &mCostSq : nullptr; }
     const DevicePtr& Dev() const { return mDev; }
 
 private:
     DevicePtr mDev;
     lgs_bb_params mParams{};
     lgs_cost_ge_params mCost{};
+    lgs_cost_sq_params mCostSq{};
+    bool mSquareError = false;
     mutable lgs_rtcsm_summary mLast{};
 };
 
@@ -264,6 +292,9 @@ public:
     ScanMatcherGridSearchHip(DevicePtr dev, const ScorePixelAccurateParams& scoreFunc,
                              const CostGreedyEndpointParams& costFunc, double rangeX, double rangeY,
                              double rangeTheta, double stepX, double stepY, double stepTheta);
+    ScanMatcherGridSearchHip(DevicePtr dev, const ScorePixelAccurateParams& scoreFunc,
+                             const CostSquareErrorParams& costFunc, double rangeX, double rangeY,
+                             double rangeTheta, double stepX, double stepY, double stepTheta);
     // OptimizePose(query): threshold DBL_MIN (:31-41)
     ScanMatchingSummary OptimizePose(const ScanMatchingQuery& queryInfo) override;
     // the const overload used by the loop detector (:44-114)
@@ -273,12 +304,16 @@ public:
     const lgs_rtcsm_summary& LastSummary() const { return mLast; }
     const lgs_gs_params& Params() const { return mParams; }
     const lgs_cost_ge_params& Cost() const { return mCost; }
+    // the square-error cost of a matcher constructed with one, else null
+    const lgs_cost_sq_params* CostSquareError() const { return mSquareError ? &mCostSq : nullptr; }
     const DevicePtr& Dev() const { return mDev; }
 
 private:
     DevicePtr mDev;
     lgs_gs_params mParams{};
     lgs_cost_ge_params mCost{};
+    lgs_cost_sq_params mCostSq{};
+    bool mSquareError = false;
     mutable lgs_rtcsm_summary mLast{};
 };
 
@@ -290,17 +325,24 @@ class ScanMatcherHillClimbingHip final : public ScanMatcher {
 public:
     ScanMatcherHillClimbingHip(DevicePtr dev, double linearStep, double angularStep, int maxIterations,
                                int maxNumOfRefinements, const CostGreedyEndpointParams& costFunc);
+    // the walk over CostSquareError (lgs_hc_sq_optimize_pose_query)
+    ScanMatcherHillClimbingHip(DevicePtr dev, double linearStep, double angularStep, int maxIterations,
+                               int maxNumOfRefinements, const CostSquareErrorParams& costFunc);
     ScanMatchingSummary OptimizePose(const ScanMatchingQuery& queryInfo) override;
     // full device summary of the last OptimizePose (best sensor pose, counters, final steps)
     const lgs_hc_summary& LastSummary() const { return mLast; }
     const lgs_hc_params& Params() const { return mParams; }
     const lgs_cost_ge_params& Cost() const { return mCost; }
+    // the square-error cost of a matcher constructed with one, else null
+    const lgs_cost_sq_params* CostSquareError() const { return mSquareError ? &mCostSq : nullptr; }
     const DevicePtr& Dev() const { return mDev; }
 
 private:
     DevicePtr mDev;
     lgs_hc_params mParams{};
     lgs_cost_ge_params mCost{};
+    lgs_cost_sq_params mCostSq{};
+    bool mSquareError = false;
     lgs_hc_summary mLast{};
 };
 

@@ -144,6 +144,11 @@ class HCSummary(C.Structure):
                 ("cost_evals", C.c_int)]
 
 
+class CostSQParams(C.Structure):
+    """lgs_cost_sq_params: CostSquareError ctor (usableRangeMin, usableRangeMax)."""
+    _fields_ = [("usable_range_min", C.c_double), ("usable_range_max", C.c_double)]
+
+
 class BuilderParams(C.Structure):
     _fields_ = [("usable_range_min", C.c_double), ("usable_range_max", C.c_double),
                 ("prob_hit", C.c_double), ("prob_miss", C.c_double)]
@@ -310,6 +315,17 @@ _PROTOS = [
                                                    C.POINTER(Pose2D), C.c_int, C.POINTER(LinsolveSummary)]),
     ("lgs_cost_square_error", C.c_int, [_P, _P, C.c_double, C.c_double, _P, Pose2D, C.POINTER(C.c_double),
                                         C.POINTER(C.c_double)]),
+    ("lgs_cost_square_error_batch", C.c_int, [_P, C.POINTER(_P), C.POINTER(CostSQParams), C.POINTER(_P),
+                                              C.POINTER(Pose2D), C.c_int, C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double)]),
+    ("lgs_summaries_apply_cost_sq", C.c_int, [_P, C.POINTER(_P), C.POINTER(CostSQParams), C.POINTER(_P),
+                                              C.POINTER(RtcsmSummary), C.c_int]),
+    ("lgs_hc_sq_optimize_pose_query", C.c_int, [_P, _P, C.POINTER(HCParams), C.POINTER(CostSQParams), _P, Pose2D,
+                                                C.POINTER(HCSummary)]),
+    ("lgs_hc_sq_optimize_pose_batch", C.c_int, [_P, C.POINTER(_P), C.POINTER(HCParams), C.POINTER(CostSQParams),
+                                                C.POINTER(_P), C.POINTER(Pose2D), C.c_int, C.POINTER(HCSummary)]),
+    ("lgs_hc_sq_trace", C.c_int, [_P, _P, C.POINTER(HCParams), C.POINTER(CostSQParams), _P, Pose2D,
+                                  C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]),
     ("lgs_debug_keysort", C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
     ("lgs_debug_map_rebuilds", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("lgs_debug_copy_counters", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -742,6 +758,73 @@ class Context:
         self.check(self.lib.lgs_cost_square_error(self.h, grid.h, umin, umax, scan.h, Pose2D(*sensor_pose),
                                                   C.byref(v), cov), "cost_square_error")
         return (v.value, list(cov)) if covariance else v.value
+
+    # ---- CostSquareError for every matcher ----
+    def cost_square_error_batch(self, grids, cost: "CostSQParams", scans, sensor_poses, covariance: bool = False):
+        """Cost and, with covariance=True, ComputeCovariance of item j at
+        sensor_poses[j] on grids[j] with scans[j] (a single grid or scan
+        serves every item): costs [n], or (costs, covariances [n, 9])"""
+        n = len(sensor_poses)
+        if not isinstance(grids, (list, tuple)):
+            grids = [grids] * n
+        if not isinstance(scans, (list, tuple)):
+            scans = [scans] * n
+        garr = (_P * max(1, n))(*[g.h for g in grids])
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in sensor_poses])
+        out = np.zeros(max(1, n))
+        cov = np.zeros((max(1, n), 9)) if covariance else None
+        self.check(self.lib.lgs_cost_square_error_batch(self.h, garr, C.byref(cost), sarr, poses, n, dptr(out),
+                                                        dptr(cov) if covariance else None),
+                   "cost_square_error_batch")
+        return (out[:n], cov[:n]) if covariance else out[:n]
+
+    def summaries_apply_cost_sq(self, grids, cost: "CostSQParams", scans, summaries):
+        """the summaries of rtcsm / bb / gs matches as a matcher constructed
+        with CostSquareError returns them: normalized cost and covariance at
+        best_sensor_pose replaced, every other field kept.  Returns new copies."""
+        n = len(summaries)
+        if not isinstance(grids, (list, tuple)):
+            grids = [grids] * n
+        garr = (_P * max(1, n))(*[g.h for g in grids])
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        arr = (RtcsmSummary * max(1, n))()
+        for k, s in enumerate(summaries):
+            C.memmove(C.byref(arr, k * C.sizeof(RtcsmSummary)), C.byref(s), C.sizeof(RtcsmSummary))
+        self.check(self.lib.lgs_summaries_apply_cost_sq(self.h, garr, C.byref(cost), sarr, arr, n),
+                   "summaries_apply_cost_sq")
+        return list(arr)[:n]
+
+    def hc_sq_optimize_pose_query(self, grid, params: "HCParams", cost: "CostSQParams", scan, init) -> "HCSummary":
+        out = HCSummary()
+        self.check(self.lib.lgs_hc_sq_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
+                                                          Pose2D(*init), C.byref(out)), "hc_sq_optimize_pose_query")
+        return out
+
+    def hc_sq_optimize_pose_batch(self, grids, params: "HCParams", cost: "CostSQParams", scans, inits):
+        """n independent matches; grids: one map per match (or a single map
+        for all), of any size and resolution"""
+        n = len(scans)
+        if not isinstance(grids, (list, tuple)):
+            grids = [grids] * n
+        garr = (_P * max(1, n))(*[g.h for g in grids])
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in inits])
+        out = (HCSummary * max(1, n))()
+        self.check(self.lib.lgs_hc_sq_optimize_pose_batch(self.h, garr, C.byref(params), C.byref(cost), sarr, poses,
+                                                          n, out), "hc_sq_optimize_pose_batch")
+        return list(out)[:n]
+
+    def hc_sq_trace(self, grid, params: "HCParams", cost: "CostSQParams", scan, init):
+        """(moves, costs): the accepted move (or -1) and minCost of every pass"""
+        cap = max(1, params.max_iterations)
+        moves = np.zeros(cap, dtype=np.int32)
+        costs = np.zeros(cap)
+        n = self.lib.lgs_hc_sq_trace(self.h, grid.h, C.byref(params), C.byref(cost), scan.h, Pose2D(*init),
+                                     moves.ctypes.data_as(C.POINTER(C.c_int)), dptr(costs), cap)
+        if n < 0:
+            self.check(-n, "hc_sq_trace")
+        return moves[:n].copy(), costs[:n].copy()
 
     # ---- occupancy maps (K3) ----
     def map(self, res: float, patch_size: int, ncx: int, ncy: int, center=(0.0, 0.0)) -> "Map":

@@ -3,7 +3,12 @@
 launcher_settings_default.json: steps 0.1 / 0.1, 100 iterations, 5
 refinements; the launcher's greedy-endpoint cost) with 1081-beam scans on a
 300 x 300 map of 24 scans (a map of fewer scans has no cell below the
-occupancy threshold, and the walk never moves on it).
+occupancy threshold, and the walk never moves on it).  With --cost
+square_error the same walks run over CostSquareError (usable range 0.01 / 20.0,
+launcher_settings_default.json:12-15): lgs_hc_sq_optimize_pose_query / _batch
+and, on the CPU, tests/hc_sq_oracle.py.  There a match pays the initial cost
+and the gradient sums at the best pose (five smoothed values per beam), which
+are counted as two more passes as well.
 
 Prints one JSON line per measurement:
   lone    lgs_hc_optimize_pose_query: p50 / p90 of the call, passes per match
@@ -33,6 +38,7 @@ for p in (os.path.join(ROOT, "my-lidar-graph-slam_amd"), os.path.join(ROOT, "tes
 
 HC = (0.1, 0.1, 100, 5)
 COST = (0.01, 20.0, 0.075, 0.1, 1, 0.05, 1.0)
+COST_SQ = (0.01, 20.0)
 REL = (0.1, -0.05, 0.02)
 BATCHES = (64, 256)
 
@@ -61,20 +67,24 @@ def gpu_step(args):
     cells, mx, my, ang, matches = scene_inputs(max(BATCHES))
     ctx = abi.Context(0)
     g = ctx.grid_from_array(cells, mx, my, 0.05)
-    P, cost = abi.HCParams(*HC), abi.CostGEParams(*COST)
+    P = abi.HCParams(*HC)
+    if args.cost == "square_error":
+        cost, query, batch = abi.CostSQParams(*COST_SQ), ctx.hc_sq_optimize_pose_query, ctx.hc_sq_optimize_pose_batch
+    else:
+        cost, query, batch = abi.CostGEParams(*COST), ctx.hc_optimize_pose_query, ctx.hc_optimize_pose_batch
     scans = [ctx.scan(r, ang, REL) for r, _ in matches]
     inits = [init for _, init in matches]
     # lone calls: every match once per step, the call's wall clock
     for k in range(args.warmup):
-        ctx.hc_optimize_pose_query(g, P, cost, scans[k % len(scans)], inits[k % len(scans)])
+        query(g, P, cost, scans[k % len(scans)], inits[k % len(scans)])
     lone, passes = [], []
     for k in range(args.lone):
         t0 = time.perf_counter()
-        s = ctx.hc_optimize_pose_query(g, P, cost, scans[k], inits[k])
+        s = query(g, P, cost, scans[k], inits[k])
         lone.append(time.perf_counter() - t0)
         passes.append(s.passes)
     lone_us = 1e6 * np.array(lone)
-    print(json.dumps(dict(line="lone", calls=len(lone), beams=len(ang), settings=list(HC),
+    print(json.dumps(dict(line="lone", cost=args.cost, calls=len(lone), beams=len(ang), settings=list(HC),
                           p50_us=round(float(np.percentile(lone_us, 50)), 1),
                           p90_us=round(float(np.percentile(lone_us, 90)), 1),
                           passes_mean=round(float(np.mean(passes)), 2), passes_min=int(min(passes)),
@@ -82,7 +92,7 @@ def gpu_step(args):
                           p50_us_per_pass=round(float(np.percentile(lone_us / (np.array(passes) + 2), 50)), 2))),
           flush=True)
     for n in BATCHES:
-        call = lambda: ctx.hc_optimize_pose_batch(g, P, cost, scans[:n], inits[:n])
+        call = lambda: batch(g, P, cost, scans[:n], inits[:n])
         for _ in range(args.warmup):
             out = call()
         t = []
@@ -92,7 +102,7 @@ def gpu_step(args):
             t.append(time.perf_counter() - t0)
         wall = float(np.median(t))
         tot = sum(o.passes + 2 for o in out)
-        print(json.dumps(dict(line="batch", matches=n, beams=len(ang), call_ms=round(1e3 * wall, 3),
+        print(json.dumps(dict(line="batch", cost=args.cost, matches=n, beams=len(ang), call_ms=round(1e3 * wall, 3),
                               matches_per_s=round(n / wall, 1), us_per_match=round(1e6 * wall / n, 2),
                               passes_mean=round(float(np.mean([o.passes for o in out])), 2),
                               passes_max=int(max(o.passes for o in out)),
@@ -106,6 +116,7 @@ def cpu_line(args):
     """the reference's loop over the oracle's pinned cost, on this CPU"""
     import oracle_bind as ob
     from hc_oracle import compose_hc
+    from hc_sq_oracle import compose_hc_sq
     cells, mx, my, ang, matches = scene_inputs(args.cpu_walks)
     g = ob.OGrid(cells, mx, my, 0.05)
     cost = ob.CostGE(*COST)
@@ -113,11 +124,14 @@ def cpu_line(args):
     for r, init in matches:
         sc = ob.OScan(r, ang, REL)
         t0 = time.perf_counter()
-        ref = compose_hc(g, cost, sc, init, REL, *HC)
+        if args.cost == "square_error":
+            ref = compose_hc_sq(g, sc, init, REL, *HC, usable=COST_SQ)
+        else:
+            ref = compose_hc(g, cost, sc, init, REL, *HC)
         t.append(time.perf_counter() - t0)
         passes.append(ref.passes)
     ms = 1e3 * np.array(t)
-    print(json.dumps(dict(line="cpu", walks=len(t), beams=len(ang), p50_ms=round(float(np.percentile(ms, 50)), 3),
+    print(json.dumps(dict(line="cpu", cost=args.cost, walks=len(t), beams=len(ang), p50_ms=round(float(np.percentile(ms, 50)), 3),
                           walks_per_s=round(len(t) / float(np.sum(t)), 1),
                           passes_mean=round(float(np.mean(passes)), 2),
                           us_per_pass=round(1e3 * float(np.sum(ms)) / float(np.sum(np.array(passes) + 2)), 1))),
@@ -132,13 +146,15 @@ def main():
     ap.add_argument("--cpu-walks", type=int, default=64)
     ap.add_argument("--timeout", type=float, default=240.0, help="time limit of the GPU step (s)")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cost", choices=["greedy_endpoint", "square_error"], default="greedy_endpoint",
+                    help="the matcher's cost function")
     ap.add_argument("--step", choices=["gpu"], help=argparse.SUPPRESS)   # child mode
     args = ap.parse_args()
     if args.step:
         gpu_step(args)
         return 0
     cmd = [sys.executable, os.path.abspath(__file__), "--step", "gpu", "--lone", str(args.lone), "--steps",
-           str(args.steps), "--warmup", str(args.warmup)]
+           str(args.steps), "--warmup", str(args.warmup), "--cost", args.cost]
     try:
         rc = subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
