@@ -20,6 +20,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_gs
 	$(MAKE) -C tests/cpp_hc
 	$(MAKE) -C tests/cpp_hc_sq
+	$(MAKE) -C tests/cpp_pgcg
 
 clean:
 	$(MAKE) -C my-lidar-graph-slam_amd/csrc clean
@@ -30,5 +31,6 @@ clean:
 	$(MAKE) -C tests/cpp_gs clean
 	$(MAKE) -C tests/cpp_hc clean
 	$(MAKE) -C tests/cpp_hc_sq clean
+	$(MAKE) -C tests/cpp_pgcg clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean

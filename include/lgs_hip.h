@@ -197,6 +197,7 @@ int  lgs_abi_version(void);
 #define LGS_OPT_ZERO_TILES    33  /* 1 (default) = the per-map passes of a correlative batch skip the stores of a tile whose inputs are all +0 when that set's buffer already holds the tile's +0 outputs (per-tile words kept per bank, set and layout); 0 = every tile stored */
 #define LGS_OPT_DEVICE_TIMING 34  /* 1 = while LGS_OPT_PROFILE(_MASK) times a kernel of a correlative batch chunk, time it on the device instead of with stream events: its workgroups stamp s_memrealtime (100 MHz) at start and end into per-chunk words (two relaxed atomic maxima per workgroup), copied back with the chunk's records; a launch's time is its first workgroup's start to its last workgroup's end (the execution span rocprofv3 reports, not the wait of a stream event for the CUs).  Launches outside a chunk's main chain keep event timing.  0 (default) = events */
 #define LGS_OPT_LEAN_PROJECT  35  /* 1 (default) = batched pruned correlative chunks (work list, wide seed, staged fine evaluation) write only the superblock base of every (angle, beam) plus per-beam / per-angle trig tables, and the kernels that stage a coarse-base or cell row form it themselves with the projection's own arithmetic (bit-identical); 0 = every row materialised (the guard fix-up reruns and lone matches always materialise) */
+#define LGS_OPT_PGCG_GRID_NODES 36 /* lgs_pg_cg_solve: systems of at least this many nodes run over many workgroups, two launches per CG pass (default 1280: up to there the vectors of the one-workgroup solve fit LDS and it is the faster one); smaller ones in one persistent workgroup.  0 = always the grid, 2^31 - 1 = never */
 #define LGS_OPT_POISON_WS     15  /* diagnostics: 1 = fill every match workspace and record with 0xFF bytes before the batch runs (any read-before-write shows up) */
 int  lgs_ctx_set_option(lgs_ctx* ctx, int option, double value);
 
@@ -818,6 +819,43 @@ int  lgs_hc_sq_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* const* grids, c
                                    const lgs_pose2d* initial_poses, int n, lgs_hc_summary* out);
 int  lgs_hc_sq_trace(lgs_ctx* ctx, const lgs_grid* grid, const lgs_hc_params* params, const lgs_cost_sq_params* cost,
                      const lgs_scan* scan, lgs_pose2d initial_pose, int* moves, double* costs, int cap);
+
+/* ---- the pose graph's conjugate-gradient step (k_pgcg.hip) ----
+ * H x = rhs for the symmetric matrix of a pose-graph Levenberg-Marquardt step
+ * (PoseGraphOptimizerLM::OptimizeStep, C/mapping/pose_graph_optimizer_lm.cpp:
+ * 175-207 with SolverType::ConjugateGradient), 3x3 blocks over num_nodes nodes:
+ * diag[v] is the block (v, v), off[p] the block (a, b) of pairs[p] = (a, b),
+ * a < b, every pair listed once; the block (b, a) is its transpose.  The solver
+ * is Eigen's ConjugateGradient recurrence with its Jacobi preconditioner (1 / d,
+ * 1 where d == 0) from a zero initial guess: it stops after the pass that
+ * brings |r|^2 below max(tolerance^2 |rhs|^2, DBL_MIN), or after
+ * max_iterations passes.  tolerance 0 selects DBL_EPSILON and max_iterations 0
+ * selects 2 * 3 num_nodes, Eigen's defaults.  *iterations receives the passes
+ * run (0 for a zero right-hand side, whose solution is x = 0) and
+ * *residual_norm2 the last |r|^2.  Systems below LGS_OPT_PGCG_GRID_NODES
+ * nodes are solved by one persistent workgroup in one launch and one stream
+ * synchronisation; larger ones over many workgroups that meet at kernel
+ * boundaries only, two launches per pass, enqueued in chunks of 32 passes
+ * with one event wait per chunk.  Either way the summation order is fixed by
+ * the node count, so a system gives the same bytes in every run and on every
+ * context (the two variants differ from each other, and from a serial sum, in
+ * the last bits); a system that holds a NaN runs to the cap and returns LGS_OK
+ * with NaNs in x.  The block pattern is built and uploaded when the pair list
+ * differs from the previous call's on this context, the values and the
+ * right-hand side on every call.
+ * LGS_ERR_INVALID_ARG, before any device work: a NULL argument (pairs and off
+ * may be NULL when num_pairs is 0), num_nodes < 1 or > 2^27, num_pairs < 0 or
+ * > 2^27, a pair with an index outside [0, num_nodes), with a >= b or listed
+ * twice, a tolerance that is negative or not finite, max_iterations < 0. */
+int  lgs_pg_cg_solve(lgs_ctx* ctx, int num_nodes, const double* diag /*[n][9] row-major*/,
+                     int num_pairs, const int* pairs /*[p][2], a < b, unique*/, const double* off /*[p][9], block (a,b)*/,
+                     const double* rhs /*[3n]*/, double tolerance /*0: DBL_EPSILON*/, int max_iterations /*0: 2*3n*/,
+                     double* x /*[3n]*/, int* iterations, double* residual_norm2);
+/* Counters of lgs_pg_cg_solve on this context since its creation: solves, CG
+ * passes over all of them, block patterns built, solves that ran over many
+ * workgroups (each may be NULL). */
+int  lgs_pg_cg_stats(const lgs_ctx* ctx, long long* solves, long long* iterations, long long* patterns,
+                     long long* grid_solves);
 
 #ifdef __cplusplus
 }

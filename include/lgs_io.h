@@ -9,6 +9,7 @@
  *                               C/io/carmen/carmen_reader.cpp:11-530
  *   lgs_pose_graph_optimize_lm  Mapping::PoseGraphOptimizerLM::Optimize
  *                               C/mapping/pose_graph_optimizer_lm.cpp:13-338
+ *   lgs_pose_graph_optimize_lm_device  the same with the ConjugateGradient solve on the GPU
  *   lgs_robust_loss             Mapping::Loss{Huber,Cauchy,Fair,GemanMcClure,Welsch,DCS,Squared}
  *                               C/mapping/robust_loss_function.cpp:17-188
  *   lgs_map_draw_image          IO::MapSaver::SaveMapCore's image (DrawMap + DrawTrajectory
@@ -74,6 +75,18 @@ typedef struct {
 int lgs_pose_graph_optimize_lm(lgs_pose_graph_lm_params* params, lgs_pose2d* node_poses, int num_nodes,
                                const lgs_pose_graph_edge* edges, int num_edges, int* iterations,
                                double* total_error);
+
+/* The same Optimize with the ConjugateGradient solve of every step on ctx's
+ * GPU (lgs_pg_cg_solve, include/lgs_hip.h): linearisation, pose update and
+ * error stay on the host and in the same arithmetic, the solve's sums run in
+ * a fixed parallel order, so poses agree with lgs_pose_graph_optimize_lm to
+ * rounding (1e-9 in the tests), not bitwise.  With LGS_LM_SPARSE_CHOLESKY the
+ * device is not used and the result is that function's, byte for byte.  The
+ * block pattern goes to the device once per call; every step uploads H's
+ * values and the right-hand side and downloads the increment. */
+int lgs_pose_graph_optimize_lm_device(lgs_ctx* ctx, lgs_pose_graph_lm_params* params, lgs_pose2d* node_poses,
+                                      int num_nodes, const lgs_pose_graph_edge* edges, int num_edges, int* iterations,
+                                      double* total_error);
 
 /* out[2i] = Loss(t[i]), out[2i+1] = Weight(t[i]) of loss `kind` (LGS_LOSS_*) */
 int lgs_robust_loss(int kind, double scale, const double* t, int n, double* out);

@@ -160,6 +160,11 @@ void* lgs_ctx::ensure_pinned_up(size_t bytes)
                 : grow_pinned(stream, pinned_up, pinned_up_bytes, bytes, true);
 }
 
+void* lgs_ctx::ensure_pinned_pg(size_t bytes)
+{
+    return grow_pinned(stream, pinned_pg, pinned_pg_bytes, bytes, false);
+}
+
 int* lgs_ctx::tedge_buffer(size_t n)
 {
     // kTedgeCtrs wrap-around counters (k_match_small) ahead of the stamps:
@@ -368,6 +373,13 @@ void lgs_ctx::release()
     pinned_up = nullptr;
     if (pinned_in) hipHostFree(pinned_in);
     pinned_in = nullptr;
+    for (auto& e : pg_ev) {
+        if (e) hipEventDestroy(e);
+        e = nullptr;
+    }
+    if (pinned_pg) hipHostFree(pinned_pg);
+    pinned_pg = nullptr;
+    pg_cache.reset();
     if (pinned_up_b) hipHostFree(pinned_up_b);
     pinned_up_b = nullptr;
     for (int b = 0; b < 2; ++b) {
@@ -529,6 +541,10 @@ extern "C" int lgs_ctx_set_option(lgs_ctx* ctx, int option, double value)
     case LGS_OPT_DEVICE_HITS: ctx->device_hits = value != 0.0; return LGS_OK;
     case LGS_OPT_ZERO_TILES: ctx->zero_tiles = value != 0.0; return LGS_OK;
     case LGS_OPT_LEAN_PROJECT: ctx->lean_project = value != 0.0; return LGS_OK;
+    case LGS_OPT_PGCG_GRID_NODES:
+        if (!(value >= 0.0)) return LGS_ERR_INVALID_ARG;
+        ctx->pg_grid_nodes = (int)std::min(value, 2147483647.0);
+        return LGS_OK;
     case LGS_OPT_SEED_WIDE:
         if (!(value >= 0.0 && value <= 16.0)) return LGS_ERR_INVALID_ARG;
         ctx->seed_wide = (int)value;

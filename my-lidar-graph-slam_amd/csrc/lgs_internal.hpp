@@ -89,6 +89,7 @@ enum Slot {
     S_ZTILE,        // unsigned: zero-tile words of the per-map passes (k_rtcsm.hip ZeroTiles), per set
     S_GS0, S_GS1,   // grid search (k_gs.hip): trig / index tables; partials, results, error word
     S_HC0, S_HC1,   // hill climbing (k_hc.hip, k_hc_sq.hip): global term rows; records, trace, error word
+    S_PG0, S_PG1,   // pose-graph CG (k_pgcg.hip): the block pattern; values, right-hand side, vectors, result
     // bank 1 of the per-batch buffers: a batched call keeps two 64-query
     // chunks in flight (the next chunk's launches go out before the host
     // finishes the previous one), each in its own bank (lgs_ctx::banked)
@@ -421,6 +422,16 @@ struct lgs_ctx {
     bool scan_ev_live[2] = {};
     void* pinned_in = nullptr;   // staging of lgs_grid_upload_patches
     size_t pinned_in_bytes = 0;
+    // lgs_pg_cg_solve (k_pgcg.hip): staging of a solve's values and right-hand
+    // side, the pattern of the last pair list (kept while the list repeats, as
+    // it does over the steps of one Optimize) and the counters of lgs_pg_cg_stats
+    void* pinned_pg = nullptr;
+    size_t pinned_pg_bytes = 0;
+    void* ensure_pinned_pg(size_t bytes);
+    std::shared_ptr<void> pg_cache;
+    long long pg_solves = 0, pg_iterations = 0, pg_patterns = 0, pg_grid_solves = 0;
+    int pg_grid_nodes = 1280;    // graphs from this many nodes on solve over many workgroups (LGS_OPT_PGCG_GRID_NODES)
+    hipEvent_t pg_ev[2] = {};    // the multi-workgroup solve's chunk records
     // padded phase-plane buffer (per bank): margins zeroed once per (buffer, layout, set count)
     void* planes_ptr[2] = {};
     int planes_sets[2] = {};

@@ -118,9 +118,11 @@ extern "C" long long lgs_carmen_load(const char* text, double* out, long long ca
     }
 }
 
-extern "C" int lgs_pose_graph_optimize_lm(lgs_pose_graph_lm_params* p, lgs_pose2d* poses, int n,
-                                          const lgs_pose_graph_edge* edges, int m, int* iterations,
-                                          double* total_error)
+namespace {
+
+// Optimize over the C arrays; dev null: both solvers on the host
+int optimize_lm(const DevicePtr& dev, lgs_pose_graph_lm_params* p, lgs_pose2d* poses, int n,
+                const lgs_pose_graph_edge* edges, int m, int* iterations, double* total_error)
 {
     if (!p || n < 0 || m < 0 || (n > 0 && !poses) || (m > 0 && !edges) || p->num_iterations_max < 0)
         return LGS_ERR_INVALID_ARG;
@@ -128,10 +130,12 @@ extern "C" int lgs_pose_graph_optimize_lm(lgs_pose_graph_lm_params* p, lgs_pose2
         auto loss = Mapping::CreateLossFunction(p->loss_kind, p->loss_scale);
         if (!loss || (p->solver != LGS_LM_SPARSE_CHOLESKY && p->solver != LGS_LM_CONJUGATE_GRADIENT))
             return LGS_ERR_INVALID_ARG;
-        Mapping::PoseGraphOptimizerLM opt(p->solver == LGS_LM_SPARSE_CHOLESKY
-                                              ? Mapping::PoseGraphOptimizerLM::SolverType::SparseCholesky
-                                              : Mapping::PoseGraphOptimizerLM::SolverType::ConjugateGradient,
-                                          p->num_iterations_max, p->error_tolerance, p->lambda, loss);
+        const auto solver = p->solver == LGS_LM_SPARSE_CHOLESKY
+                                ? Mapping::PoseGraphOptimizerLM::SolverType::SparseCholesky
+                                : Mapping::PoseGraphOptimizerLM::SolverType::ConjugateGradient;
+        Mapping::PoseGraphOptimizerLM opt =
+            dev ? Mapping::PoseGraphOptimizerLM(dev, solver, p->num_iterations_max, p->error_tolerance, p->lambda, loss)
+                : Mapping::PoseGraphOptimizerLM(solver, p->num_iterations_max, p->error_tolerance, p->lambda, loss);
         std::vector<Mapping::PoseGraph::Node> nodes;
         nodes.reserve((size_t)n);
         for (int i = 0; i < n; ++i) nodes.emplace_back(i, RobotPose2D<double>(poses[i].x, poses[i].y, poses[i].theta));
@@ -146,6 +150,23 @@ extern "C" int lgs_pose_graph_optimize_lm(lgs_pose_graph_lm_params* p, lgs_pose2
         if (total_error) *total_error = opt.LastTotalError();
         return LGS_OK;
     });
+}
+
+}  // namespace
+
+extern "C" int lgs_pose_graph_optimize_lm(lgs_pose_graph_lm_params* p, lgs_pose2d* poses, int n,
+                                          const lgs_pose_graph_edge* edges, int m, int* iterations,
+                                          double* total_error)
+{
+    return optimize_lm(nullptr, p, poses, n, edges, m, iterations, total_error);
+}
+
+extern "C" int lgs_pose_graph_optimize_lm_device(lgs_ctx* ctx, lgs_pose_graph_lm_params* p, lgs_pose2d* poses, int n,
+                                                 const lgs_pose_graph_edge* edges, int m, int* iterations,
+                                                 double* total_error)
+{
+    if (!ctx) return LGS_ERR_INVALID_ARG;
+    return optimize_lm(std::make_shared<Device>(ctx), p, poses, n, edges, m, iterations, total_error);
 }
 
 extern "C" int lgs_robust_loss(int kind, double scale, const double* t, int n, double* out)

@@ -511,8 +511,27 @@ void PoseGraphOptimizerLM::OptimizeStep(std::vector<PoseGraph::Node>& nodes,
         for (int k = 0; k < 3; ++k) H.diag[v][4 * k] += mLambda;
     std::vector<double> rhs(b.size());
     for (size_t i = 0; i < b.size(); ++i) rhs[i] = -b[i];
-    const std::vector<double> delta =
-        (mSolverType == SolverType::SparseCholesky) ? solve_cholesky(H, rhs) : solve_cg(H, rhs);
+    std::vector<double> delta;
+    if (mSolverType == SolverType::SparseCholesky) {
+        delta = solve_cholesky(H, rhs);
+    } else if (!mDev) {
+        delta = solve_cg(H, rhs);
+    } else if (n > 0) {
+        // the same recurrence on the device, Eigen's default tolerance and cap.
+        // The pair list repeats over the steps of an Optimize (it follows the
+        // edge list), so the library uploads the block pattern once
+        static_assert(sizeof(Mat3) == 9 * sizeof(double) && sizeof(std::pair<int, int>) == 2 * sizeof(int),
+                      "blocks and pairs are handed over as flat arrays");
+        delta.resize(rhs.size());
+        int iterations = 0;
+        double residual = 0.0;
+        mDev->Check(lgs_pg_cg_solve(mDev->Handle(), n, H.diag[0].data(), (int)H.pairs.size(),
+                                    H.pairs.empty() ? nullptr : &H.pairs[0].first,
+                                    H.off.empty() ? nullptr : H.off[0].data(), rhs.data(), 0.0, 0, delta.data(),
+                                    &iterations, &residual),
+                    "lgs_pg_cg_solve");
+        mLastSolverIterations += iterations;
+    }
     for (int i = 0; i < n; ++i) {   // :209-217
         const RobotPose2D<double>& p = nodes.at(i).Pose();
         nodes.at(i).Pose() =
@@ -529,6 +548,7 @@ void PoseGraphOptimizerLM::Optimize(std::vector<PoseGraph::Node>& nodes, const s
     double prevTotalError = std::numeric_limits<double>::max();
     double totalError = std::numeric_limits<double>::max();
     int numOfIterations = 0;
+    mLastSolverIterations = 0;
     while (true) {
         OptimizeStep(nodes, edges);
         totalError = ComputeTotalError(nodes, edges);

@@ -11,11 +11,15 @@
 // The pose graph is a sparse nonlinear least-squares problem over 3-vectors
 // (Sparse Pose Adjustment): a few thousand nodes, each linked to its
 // neighbours and a handful of loop edges.  It is not a grid workload and its
-// factorisation is a chain of small dependent 3x3 block operations, so it
-// stays on the host: the reference's Eigen SimplicialLDLT is
-// replaced by a block (3x3) sparse Cholesky with a minimum-degree node
-// ordering, and Eigen's ConjugateGradient by the same Jacobi-preconditioned
-// CG recurrence.  No Eigen: matrices are row-major std::array.
+// factorisation is a chain of small dependent 3x3 block operations, so the
+// linearisation and the Cholesky solve stay on the host: the
+// reference's Eigen SimplicialLDLT is replaced by a block (3x3) sparse
+// Cholesky with a minimum-degree node ordering, and Eigen's ConjugateGradient
+// by the same Jacobi-preconditioned CG recurrence.  An optimizer constructed
+// with a Device runs that recurrence on the GPU instead (lgs_pg_cg_solve,
+// DESIGN.md §4.7b): thousands of strictly sequential passes over a sparse
+// matrix-vector product, which one workgroup walks far faster than a host
+// core.  No Eigen: matrices are row-major std::array.
 #pragma once
 
 #include <array>
@@ -134,6 +138,15 @@ public:
                          LossFunctionPtr lossFunction)
         : mSolverType(solverType), mNumOfIterationsMax(numOfIterationsMax), mErrorTolerance(errorTolerance),
           mLambda(initialLambda), mLossFunction(std::move(lossFunction)) {}
+    // The same optimizer with the ConjugateGradient solve on `dev`
+    // (lgs_pg_cg_solve: the same recurrence, its sums in a fixed parallel
+    // order, so poses agree with the host solve to rounding, not bitwise).
+    // The linearisation, the pose update and the error stay on the host, and
+    // SolverType::SparseCholesky behaves exactly as without a device.
+    PoseGraphOptimizerLM(DevicePtr dev, SolverType solverType, int numOfIterationsMax, double errorTolerance,
+                         double initialLambda, LossFunctionPtr lossFunction)
+        : mSolverType(solverType), mNumOfIterationsMax(numOfIterationsMax), mErrorTolerance(errorTolerance),
+          mLambda(initialLambda), mLossFunction(std::move(lossFunction)), mDev(std::move(dev)) {}
 
     // C/mapping/pose_graph_optimizer_lm.cpp:13-65.  The damping factor is a
     // member and carries over to the next call, as in the reference.
@@ -148,6 +161,8 @@ public:
     double Lambda() const { return mLambda; }
     int LastIterations() const { return mLastIterations; }
     double LastTotalError() const { return mLastTotalError; }
+    // CG passes of the device solves of the last Optimize, all steps together (0 without a device)
+    long long LastSolverIterations() const { return mLastSolverIterations; }
 
 private:
     // :68-220: H and b from every edge, the 1e9 anchor on node 0, lambda on the
@@ -161,6 +176,8 @@ private:
     LossFunctionPtr mLossFunction;
     int mLastIterations = 0;
     double mLastTotalError = 0.0;
+    DevicePtr mDev;   // null: both solvers on the host
+    long long mLastSolverIterations = 0;
 };
 
 }  // namespace Mapping

@@ -41,7 +41,7 @@ Device::Device(int device)
 
 Device::~Device()
 {
-    if (mCtx) lgs_ctx_destroy(mCtx);
+    if (mCtx && mOwned) lgs_ctx_destroy(mCtx);
 }
 
 void Device::Check(int status, const char* what) const

@@ -69,6 +69,8 @@ struct Matrix3d {
 class Device {
 public:
     explicit Device(int device = 0);
+    // a context the caller created and keeps (the C entry points of lgs_io.h): not destroyed here
+    explicit Device(lgs_ctx* borrowed) : mCtx(borrowed), mOwned(false) {}
     ~Device();
     Device(const Device&) = delete;
     Device& operator=(const Device&) = delete;
@@ -78,6 +80,7 @@ public:
 
 private:
     lgs_ctx* mCtx = nullptr;
+    bool mOwned = true;
 };
 using DevicePtr = std::shared_ptr<Device>;
 

@@ -46,6 +46,7 @@ LGS_OPT_SEED_WIDE = 32
 LGS_OPT_ZERO_TILES = 33
 LGS_OPT_DEVICE_TIMING = 34   # correlative chunks' kernels timed on the device (s_memrealtime spans)
 LGS_OPT_LEAN_PROJECT = 35    # batched chunks: only superblock bases projected; consumers form their rows
+LGS_OPT_PGCG_GRID_NODES = 36  # lgs_pg_cg_solve: node count from which the solve runs over many workgroups
 KERNEL_IDS = ["k_project", "k_coarse", "k_seed", "k_select", "k_fine", "k_replay", "k_cost", "k_precompute",
               "k_linsolve", "k_ray_emit", "k_ray_apply", "k_super", "k_super_planes", "k_bb_score",
               "k_bb_expand", "k_coarse_aux", "k_match_small", "k_gs_score"]   # lgs_ctx_kernel_stats order
@@ -326,6 +327,11 @@ _PROTOS = [
                                                 C.POINTER(_P), C.POINTER(Pose2D), C.c_int, C.POINTER(HCSummary)]),
     ("lgs_hc_sq_trace", C.c_int, [_P, _P, C.POINTER(HCParams), C.POINTER(CostSQParams), _P, Pose2D,
                                   C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]),
+    ("lgs_pg_cg_solve", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
+                                  C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("lgs_pg_cg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                  C.POINTER(C.c_longlong)]),
     ("lgs_debug_keysort", C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
     ("lgs_debug_map_rebuilds", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("lgs_debug_copy_counters", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -827,6 +833,31 @@ class Context:
         return moves[:n].copy(), costs[:n].copy()
 
     # ---- occupancy maps (K3) ----
+    def pg_cg_solve(self, diag, pairs, off, rhs, tolerance: float = 0.0, max_iterations: int = 0):
+        """lgs_pg_cg_solve: H x = rhs of a pose-graph LM step by Jacobi-preconditioned
+        CG on the device.  diag [n, 3, 3], pairs [p, 2] (a < b, unique), off
+        [p, 3, 3] (block (a, b)), rhs [3n] -> (x [3n], passes, last |r|^2)"""
+        diag = np.ascontiguousarray(diag, dtype=np.float64).reshape(-1, 9)
+        n = diag.shape[0]
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        off = np.ascontiguousarray(off, dtype=np.float64).reshape(-1, 9)
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1)
+        assert off.shape[0] == pairs.shape[0] and rhs.shape[0] == 3 * n
+        x = np.zeros(3 * max(n, 1))
+        it, res = C.c_int(), C.c_double()
+        npairs = pairs.shape[0]
+        self.check(self.lib.lgs_pg_cg_solve(self.h, n, dptr(diag), npairs,
+                                            pairs.ctypes.data_as(C.POINTER(C.c_int)) if npairs else None,
+                                            dptr(off) if npairs else None, dptr(rhs), float(tolerance),
+                                            int(max_iterations), dptr(x), C.byref(it), C.byref(res)), "pg_cg_solve")
+        return x[:3 * n], it.value, res.value
+
+    def pg_cg_stats(self) -> dict:
+        """lgs_pg_cg_stats: solves, CG passes, block patterns built and multi-workgroup solves on this context"""
+        a, b, c, d = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
+        self.check(self.lib.lgs_pg_cg_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "pg_cg_stats")
+        return dict(solves=a.value, iterations=b.value, patterns=c.value, grid_solves=d.value)
+
     def map(self, res: float, patch_size: int, ncx: int, ncy: int, center=(0.0, 0.0)) -> "Map":
         h = _P()
         self.check(self.lib.lgs_map_create(self.h, res, patch_size, ncx, ncy, center[0], center[1],

@@ -45,6 +45,8 @@ _PROTOS = [
                                        C.POINTER(C.c_int)]),
     ("lgs_pose_graph_optimize_lm", C.c_int, [C.POINTER(LMParams), C.POINTER(Pose2D), C.c_int,
                                              C.POINTER(PoseGraphEdge), C.c_int, C.POINTER(C.c_int), _D]),
+    ("lgs_pose_graph_optimize_lm_device", C.c_int, [_P, C.POINTER(LMParams), C.POINTER(Pose2D), C.c_int,
+                                                    C.POINTER(PoseGraphEdge), C.c_int, C.POINTER(C.c_int), _D]),
     ("lgs_robust_loss", C.c_int, [C.c_int, C.c_double, _D, C.c_int, _D]),
     ("lgs_map_draw_image", C.c_int, [_P, _P, C.POINTER(Pose2D), C.c_int, C.POINTER(MapSaveOptions),
                                      C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -102,17 +104,25 @@ def edges_array(edges):
 
 
 def optimize_lm(poses, edges, solver=LM_SPARSE_CHOLESKY, iters=10, tol=1e-3, lam=1e-4, loss="huber",
-                scale=1.0):
-    """PoseGraphOptimizerLM::Optimize -> (poses [n, 3], iterations, total error, lambda after)"""
+                scale=1.0, ctx: Optional["abi.Context"] = None):
+    """PoseGraphOptimizerLM::Optimize -> (poses [n, 3], iterations, total error, lambda after).
+    With a context the ConjugateGradient solve of every step runs on its device
+    (lgs_pose_graph_optimize_lm_device); edges may be an edges_array() result."""
     L = load()
     n = len(poses)
     p = (Pose2D * max(1, n))(*[Pose2D(*q) for q in poses])
     prm = LMParams(solver, iters, tol, lam, LOSSES[loss] if isinstance(loss, str) else loss, scale)
     it, tot = C.c_int(), C.c_double()
-    rc = L.lgs_pose_graph_optimize_lm(C.byref(prm), p, n, edges_array(edges), len(edges), C.byref(it),
-                                      C.byref(tot))
+    if isinstance(edges, C.Array):
+        earr, m = edges, len(edges)
+    else:
+        earr, m = edges_array(edges), len(edges)
+    if ctx is None:
+        rc = L.lgs_pose_graph_optimize_lm(C.byref(prm), p, n, earr, m, C.byref(it), C.byref(tot))
+    else:
+        rc = L.lgs_pose_graph_optimize_lm_device(ctx.h, C.byref(prm), p, n, earr, m, C.byref(it), C.byref(tot))
     if rc != 0:
-        raise RuntimeError(f"lgs_pose_graph_optimize_lm: status {rc}")
+        raise RuntimeError(f"lgs_pose_graph_optimize_lm{'' if ctx is None else '_device'}: status {rc}")
     return np.array([[q.x, q.y, q.theta] for q in p[:n]]), it.value, tot.value, prm.lambda_
 
 
