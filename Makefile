@@ -21,6 +21,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_hc
 	$(MAKE) -C tests/cpp_hc_sq
 	$(MAKE) -C tests/cpp_pgcg
+	$(MAKE) -C tests/cpp_pglm
 
 clean:
 	$(MAKE) -C my-lidar-graph-slam_amd/csrc clean
@@ -32,5 +33,6 @@ clean:
 	$(MAKE) -C tests/cpp_hc clean
 	$(MAKE) -C tests/cpp_hc_sq clean
 	$(MAKE) -C tests/cpp_pgcg clean
+	$(MAKE) -C tests/cpp_pglm clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean

@@ -213,7 +213,9 @@ int  lgs_debug_item_buffer(lgs_ctx* ctx, int item, int which, void* out, size_t 
 /* Diagnostics: the device's restatements of glibc's sincos() (op 0: out[2i] =
  * sin x[i], out[2i+1] = cos x[i]) and pow(x, 3.0) (op 1: out[i]) evaluated on
  * the GPU for n host inputs (csrc/glibc_math.hpp; tests compare them with the
- * host libm bit for bit). */
+ * host libm bit for bit).  Ops 2 and 3 are the device's own sqrt(x[i]) and
+ * fmod(x[i], 2 pi), which the pose-graph linearisation (k_pglm.hip) relies on
+ * being the host's bits. */
 int  lgs_debug_libm(lgs_ctx* ctx, int op, const double* x, int n, double* out);
 
 /* Diagnostics: the K3 sort (csrc/k_sort.hip, the stable radix sort behind
@@ -856,6 +858,59 @@ int  lgs_pg_cg_solve(lgs_ctx* ctx, int num_nodes, const double* diag /*[n][9] ro
  * workgroups (each may be NULL). */
 int  lgs_pg_cg_stats(const lgs_ctx* ctx, long long* solves, long long* iterations, long long* patterns,
                      long long* grid_solves);
+
+/* ---- the pose graph's Levenberg-Marquardt loop, resident on the device
+ * (k_pglm.hip) ----
+ * PoseGraphOptimizerLM::Optimize (C/mapping/pose_graph_optimizer_lm.cpp:13-338)
+ * with SolverType::ConjugateGradient and every step on the device: poses and
+ * edges go up once, each step linearises every edge (k_pg_linearise writes H
+ * straight into the layout the solve walks, and rhs = -b), solves as
+ * lgs_pg_cg_solve does (Eigen's defaults; counted by lgs_pg_cg_stats), adds
+ * the increment to the poses and evaluates Loss(e^T Lambda e) per edge; the
+ * host adds those terms in edge order and applies Optimize's rule for the
+ * damping factor and for stopping.  The poses come down once at the end.
+ * Every entry of H and b is the sequential sum in edge order that the host's
+ * OptimizeStep forms, in its arithmetic (glibc's sincos restated, IEEE
+ * division and square root, no contraction), so for the losses whose Weight is
+ * IEEE-only (all but Welsch, whose exp is the device's) the system, and with
+ * it every pose, equals lgs_pose_graph_optimize_lm_device's byte for byte; the
+ * total error does for the losses whose Loss is IEEE-only too (Huber,
+ * GemanMcClure, DCS, Squared).
+ * LGS_ERR_INVALID_ARG, before any device work: a NULL argument (edges may be
+ * NULL when m is 0), n < 1 or > 2^27, m < 0 or > 2^27, an edge index outside
+ * [0, n), a loss kind outside 0..6, a damping factor, tolerance or scale that
+ * is not finite.  LGS_ERR_INTERNAL when a finite start-node angle leaves the
+ * restated sincos's domain (|theta| >= 105414350).  The caller's poses are
+ * written only by a call that returns LGS_OK.  A NaN pose is no error: the
+ * solves run to their cap and NaNs come back. */
+/* PoseGraph::Edge: the layout of lgs_pose_graph_edge (include/lgs_io.h) */
+typedef struct {
+    int start_node_index, end_node_index;
+    lgs_pose2d relative_pose;
+    double information[9];          /* row-major 3x3 */
+} lgs_pg_edge;
+typedef struct {
+    int num_iterations_max;         /* at least one step runs whatever this is, as in the reference */
+    double error_tolerance;
+    int loss_kind;                  /* 0 Huber, 1 Cauchy, 2 Fair, 3 GemanMcClure, 4 Welsch, 5 DCS, 6 Squared (LGS_LOSS_*) */
+    double loss_scale;
+} lgs_pg_lm_params;
+/* *lambda: in, the damping factor; out, what Optimize leaves for the next call.
+ * *iterations LM steps, *total_error after the last, *cg_passes over all solves. */
+int  lgs_pg_lm_optimize(lgs_ctx* ctx, const lgs_pg_lm_params* params, double* lambda /*in/out*/, lgs_pose2d* poses,
+                        int n, const lgs_pg_edge* edges, int m, int* iterations, double* total_error,
+                        long long* cg_passes);
+/* Diagnostics: the device's H and right-hand side of one step at the given
+ * poses.  *num_pairs pairs (a, b), a < b, in the order the edges first name
+ * them (at most m: size pairs and off for m); off[p] is the block (a, b). */
+int  lgs_pg_lm_linearize(lgs_ctx* ctx, int loss_kind, double loss_scale, double lambda, const lgs_pose2d* poses, int n,
+                         const lgs_pg_edge* edges, int m, double* diag /*[n][9]*/, int* num_pairs,
+                         int* pairs /*[<= m][2]*/, double* off /*[<= m][9]*/, double* rhs /*[3n]*/);
+/* Counters of lgs_pg_lm_optimize on this context since its creation: calls
+ * that ran, LM steps, uploads and downloads of the poses, incidence-list
+ * builds (each may be NULL). */
+int  lgs_pg_lm_stats(const lgs_ctx* ctx, long long* optimizes, long long* steps, long long* pose_uploads,
+                     long long* pose_downloads, long long* incidence_builds);
 
 #ifdef __cplusplus
 }

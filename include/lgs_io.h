@@ -10,6 +10,8 @@
  *   lgs_pose_graph_optimize_lm  Mapping::PoseGraphOptimizerLM::Optimize
  *                               C/mapping/pose_graph_optimizer_lm.cpp:13-338
  *   lgs_pose_graph_optimize_lm_device  the same with the ConjugateGradient solve on the GPU
+ *   lgs_pose_graph_optimize_lm_resident  the same with every step on the GPU (lgs_pg_lm_optimize)
+ *   lgs_pose_graph_linearize    the H and right-hand side OptimizeStep solves (:68-172)
  *   lgs_robust_loss             Mapping::Loss{Huber,Cauchy,Fair,GemanMcClure,Welsch,DCS,Squared}
  *                               C/mapping/robust_loss_function.cpp:17-188
  *   lgs_map_draw_image          IO::MapSaver::SaveMapCore's image (DrawMap + DrawTrajectory
@@ -83,10 +85,38 @@ int lgs_pose_graph_optimize_lm(lgs_pose_graph_lm_params* params, lgs_pose2d* nod
  * rounding (1e-9 in the tests), not bitwise.  With LGS_LM_SPARSE_CHOLESKY the
  * device is not used and the result is that function's, byte for byte.  The
  * block pattern goes to the device once per call; every step uploads H's
- * values and the right-hand side and downloads the increment. */
+ * values and the right-hand side and downloads the increment
+ * (lgs_pose_graph_optimize_lm_resident keeps all of it on the device). */
 int lgs_pose_graph_optimize_lm_device(lgs_ctx* ctx, lgs_pose_graph_lm_params* params, lgs_pose2d* node_poses,
                                       int num_nodes, const lgs_pose_graph_edge* edges, int num_edges, int* iterations,
                                       double* total_error);
+
+/* The same Optimize with the pose graph resident on ctx's GPU across the
+ * steps (lgs_pg_lm_optimize, include/lgs_hip.h): poses and
+ * edges go up once, every step's linearisation, damping, conjugate-gradient
+ * solve, pose update and per-edge loss run on the device, the poses come down
+ * once; per step only the loss terms and the solve's record cross to the
+ * host, which adds the terms in edge order.  The device forms H and the
+ * right-hand side in lgs_pose_graph_linearize's arithmetic and summation
+ * order, so with every loss but LGS_LOSS_WELSCH the poses, the step count and
+ * the damping factor are lgs_pose_graph_optimize_lm_device's byte for byte
+ * (Welsch: to 1e-9), and the total error is too unless the loss calls log1p
+ * or expm1 (Cauchy, Fair, Welsch: 1e-9 relative).
+ * LGS_ERR_INVALID_ARG: LGS_LM_SPARSE_CHOLESKY (there is no host fallback), no
+ * node, and what lgs_pg_lm_optimize refuses. */
+int lgs_pose_graph_optimize_lm_resident(lgs_ctx* ctx, lgs_pose_graph_lm_params* params, lgs_pose2d* node_poses,
+                                        int num_nodes, const lgs_pose_graph_edge* edges, int num_edges, int* iterations,
+                                        double* total_error);
+
+/* The host's H and right-hand side of one step at node_poses with the damping
+ * factor params->lambda (params->solver is not read): diag[v] the block
+ * (v, v) with the 1e9 anchor on node 0 and lambda, *num_pairs pairs (a, b),
+ * a < b, in the order the edges first name them (at most num_edges: size
+ * pairs and off for that), off[p] the block (a, b), rhs = -b.  It is the code
+ * OptimizeStep runs. */
+int lgs_pose_graph_linearize(const lgs_pose_graph_lm_params* params, const lgs_pose2d* node_poses, int num_nodes,
+                             const lgs_pose_graph_edge* edges, int num_edges, double* diag /*[n][9]*/, int* num_pairs,
+                             int* pairs /*[<= m][2]*/, double* off /*[<= m][9]*/, double* rhs /*[3n]*/);
 
 /* out[2i] = Loss(t[i]), out[2i+1] = Weight(t[i]) of loss `kind` (LGS_LOSS_*) */
 int lgs_robust_loss(int kind, double scale, const double* t, int n, double* out);

@@ -1019,15 +1019,19 @@ __global__ void k_debug_libm(int op, const double* __restrict__ x, int n, double
         glm::gl_sincos(x[i], &s, &c);
         out[2 * i] = s;
         out[2 * i + 1] = c;
-    } else {
+    } else if (op == 1) {
         out[i] = glm::gl_pow3(x[i]);
+    } else if (op == 2) {
+        out[i] = sqrt(x[i]);
+    } else {
+        out[i] = fmod(x[i], 2.0 * M_PI);
     }
 }
 }  // namespace
 
 extern "C" int lgs_debug_libm(lgs_ctx* ctx, int op, const double* x, int n, double* out)
 {
-    if (!ctx || !x || !out || n < 0 || (op != 0 && op != 1)) return LGS_ERR_INVALID_ARG;
+    if (!ctx || !x || !out || n < 0 || op < 0 || op > 3) return LGS_ERR_INVALID_ARG;
     if (n == 0) return LGS_OK;
     return guarded(ctx, [&] {
         LGS_HIP_CHECK(hipSetDevice(ctx->device));

@@ -44,13 +44,6 @@ constexpr int kPgThreads = 1024;
 constexpr int kPgWaves = kPgThreads / 64;
 constexpr size_t kPgLdsMax = 152 * 1024;   // dynamic LDS of k_pgcg: all five vectors, or p alone, while they fit
 
-struct PgResult {
-    double residual_norm2;
-    double threshold;      // k_pgcg_grid_*: max(tol^2 |rhs|^2, DBL_MIN), kept from pass 0
-    int iterations;
-    int done;              // k_pgcg_grid_*: the solve has ended, later launches return at once
-};
-
 struct PgArgs {
     const int* rowptr;     // [n + 1]
     const int* col;        // [blocks]
@@ -402,8 +395,6 @@ __global__ __launch_bounds__(kPgGridThreads) void k_pgcg_grid_update(PgGridArgs 
     }
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the pattern of the pair list a context solved last
 struct PgCache {
     std::vector<int> pairs;
@@ -411,6 +402,116 @@ struct PgCache {
 };
 
 }  // namespace
+
+bool lgs::pg_runs_grid(const lgs_ctx* ctx, int num_nodes) { return num_nodes >= ctx->pg_grid_nodes; }
+
+namespace {
+int pg_grid_wgs(size_t m) { return (int)std::min<size_t>((m + kPgGridThreads - 1) / kPgGridThreads, (size_t)kPgGridMaxWgs); }
+}  // namespace
+
+size_t lgs::pg_work_bytes(const lgs_ctx* ctx, int num_nodes)
+{
+    const size_t m = 3 * (size_t)num_nodes, mb = pg_align256(sizeof(double) * m);
+    const bool in_lds = sizeof(double) * m <= kPgLdsMax;
+    const size_t gb = pg_align256(sizeof(double) * (size_t)pg_grid_wgs(m));
+    return pg_runs_grid(ctx, num_nodes) ? 6 * mb + 5 * gb : 3 * mb + (in_lds ? 0 : mb);
+}
+
+bool lgs::pg_solve_enqueue(lgs_ctx* ctx, const PgDeviceSystem& s, double tolerance, int max_iterations)
+{
+    const int num_nodes = s.n;
+    const size_t m = 3 * (size_t)num_nodes, mb = pg_align256(sizeof(double) * m);
+    const bool grid = pg_runs_grid(ctx, num_nodes);
+    const bool in_lds = sizeof(double) * m <= kPgLdsMax;
+    const int G = pg_grid_wgs(m);
+    const size_t gb = pg_align256(sizeof(double) * (size_t)G);
+    double* const d_work = s.work;
+    const size_t mw = mb / sizeof(double), gw = gb / sizeof(double);
+    const double tol2 = (tolerance == 0.0) ? DBL_EPSILON * DBL_EPSILON : tolerance * tolerance;
+    const int cap = max_iterations == 0 ? (int)(2 * m) : max_iterations;
+    if (!grid) {
+        PgArgs a;
+        a.rowptr = s.rowptr;
+        a.col = s.col;
+        a.val = s.val;
+        a.rhs = s.rhs;
+        a.x = s.x;
+        a.res = s.res;
+        a.r = d_work;
+        a.t = d_work + mw;
+        a.inv = d_work + 2 * mw;
+        a.p = in_lds ? nullptr : d_work + 3 * mw;
+        a.tol2 = tol2;
+        a.n = num_nodes;
+        a.max_iterations = cap;
+        const int mode = 5 * sizeof(double) * m <= kPgLdsMax ? 2 : in_lds ? 1 : 0;
+        const size_t lds = mode == 2 ? 5 * sizeof(double) * m : mode == 1 ? sizeof(double) * m : 0;
+        auto launch = [&](auto kernel) {
+            if (lds > 64 * 1024) {   // dynamic LDS beyond the 64 KiB default has to be announced
+                (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipGetLastError();
+            }
+            hipLaunchKernelGGL(kernel, dim3(1), dim3(kPgThreads), lds, ctx->stream, a);
+        };
+        if (mode == 2)
+            launch(k_pgcg<2>);
+        else if (mode == 1)
+            launch(k_pgcg<1>);
+        else
+            launch(k_pgcg<0>);
+        LGS_HIP_CHECK(hipGetLastError());
+    } else {
+        PgGridArgs a;
+        a.rowptr = s.rowptr;
+        a.col = s.col;
+        a.val = s.val;
+        a.rhs = s.rhs;
+        a.x = s.x;
+        a.res = s.res;
+        a.r = d_work;
+        a.z = d_work + mw;
+        a.inv = d_work + 2 * mw;
+        a.t = d_work + 3 * mw;
+        a.p[0] = d_work + 4 * mw;
+        a.p[1] = d_work + 5 * mw;
+        double* const parts = d_work + 6 * mw;
+        a.part_pt = parts;
+        a.part_rr[0] = parts + gw;
+        a.part_rr[1] = parts + 2 * gw;
+        a.part_rz[0] = parts + 3 * gw;
+        a.part_rz[1] = parts + 4 * gw;
+        a.tol2 = tol2;
+        a.n = num_nodes;
+        a.G = G;
+        for (hipEvent_t& e : ctx->pg_ev)
+            if (!e) LGS_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        LGS_HIP_CHECK(hipMemsetAsync(s.res, 0, sizeof(PgResult), ctx->stream));
+        hipLaunchKernelGGL(k_pgcg_grid_init, dim3(G), dim3(kPgGridThreads), 0, ctx->stream, a);
+        LGS_HIP_CHECK(hipGetLastError());
+        // chunks of passes; the record of chunk k is looked at once chunk k + 1 is enqueued
+        PgResult* const seen = s.seen;
+        int it = 0;
+        for (int chunk = 0;; ++chunk) {
+            const int end = (int)std::min<long long>((long long)it + kPgGridChunk, cap);
+            for (; it < end; ++it) {
+                hipLaunchKernelGGL(k_pgcg_grid_spmv, dim3(G), dim3(kPgGridThreads), 0, ctx->stream, a, it, cap);
+                hipLaunchKernelGGL(k_pgcg_grid_update, dim3(G), dim3(kPgGridThreads), 0, ctx->stream, a, it);
+            }
+            if (it == cap)   // concludes the last pass
+                hipLaunchKernelGGL(k_pgcg_grid_spmv, dim3(G), dim3(kPgGridThreads), 0, ctx->stream, a, cap, cap);
+            LGS_HIP_CHECK(hipGetLastError());
+            if (it == cap) break;
+            LGS_HIP_CHECK(hipMemcpyAsync(seen + (chunk & 1), s.res, sizeof(PgResult), hipMemcpyDeviceToHost,
+                                         ctx->stream));
+            LGS_HIP_CHECK(hipEventRecord(ctx->pg_ev[chunk & 1], ctx->stream));
+            if (chunk > 0) {
+                ctx->wait_event(ctx->pg_ev[(chunk - 1) & 1]);
+                if (seen[(chunk - 1) & 1].done) break;
+            }
+        }
+    }
+    return grid;
+}
 
 extern "C" int lgs_pg_cg_solve(lgs_ctx* ctx, int num_nodes, const double* diag, int num_pairs, const int* pairs,
                                const double* off, const double* rhs, double tolerance, int max_iterations, double* x,
@@ -438,15 +539,10 @@ extern "C" int lgs_pg_cg_solve(lgs_ctx* ctx, int num_nodes, const double* diag, 
         LGS_HIP_CHECK(hipSetDevice(ctx->device));
 
         // device layout: S_PG0 = rowptr | col, S_PG1 = val | rhs | x | result | work vectors (| partial sums)
-        const size_t rpb = align256(sizeof(int) * ((size_t)num_nodes + 1)), clb = align256(sizeof(int) * blocks);
-        const size_t vb = align256(sizeof(double) * 9 * blocks), mb = align256(sizeof(double) * m);
-        const bool grid = num_nodes >= ctx->pg_grid_nodes;
-        const bool in_lds = sizeof(double) * m <= kPgLdsMax;
-        const int G = (int)std::min<size_t>((m + kPgGridThreads - 1) / kPgGridThreads, (size_t)kPgGridMaxWgs);
-        const size_t gb = align256(sizeof(double) * (size_t)G);
-        const size_t work = grid ? 6 * mb + 5 * gb : 3 * mb + (in_lds ? 0 : mb);
+        const size_t rpb = pg_align256(sizeof(int) * ((size_t)num_nodes + 1)), clb = pg_align256(sizeof(int) * blocks);
+        const size_t vb = pg_align256(sizeof(double) * 9 * blocks), mb = pg_align256(sizeof(double) * m);
         char* d_pat = (char*)ctx->ensure(S_PG0, rpb + clb);
-        char* d_sys = (char*)ctx->ensure(S_PG1, vb + mb + mb + 256 + work);
+        char* d_sys = (char*)ctx->ensure(S_PG1, vb + mb + mb + 256 + pg_work_bytes(ctx, num_nodes));
         char* pin = (char*)ctx->ensure_pinned_pg(vb + mb + (known ? 0 : rpb + clb));
         if (!known) {
             std::memcpy(pin + vb + mb, pat.rowptr.data(), sizeof(int) * pat.rowptr.size());
@@ -458,95 +554,19 @@ extern "C" int lgs_pg_cg_solve(lgs_ctx* ctx, int num_nodes, const double* diag, 
         std::memcpy(pin + vb, rhs, sizeof(double) * m);
         LGS_HIP_CHECK(hipMemcpyAsync(d_sys, pin, vb + mb, hipMemcpyHostToDevice, ctx->stream));
 
-        double* const d_x = (double*)(d_sys + vb + mb);
-        PgResult* const d_res = (PgResult*)(d_sys + vb + 2 * mb);
-        double* const d_work = (double*)(d_sys + vb + 2 * mb + 256);
-        const size_t mw = mb / sizeof(double), gw = gb / sizeof(double);
-        const double tol2 = (tolerance == 0.0) ? DBL_EPSILON * DBL_EPSILON : tolerance * tolerance;
-        const int cap = max_iterations == 0 ? (int)(2 * m) : max_iterations;
         char* back = (char*)ctx->ensure_pinned(mb + 256 + 2 * sizeof(PgResult));
-        if (!grid) {
-            PgArgs a;
-            a.rowptr = (const int*)d_pat;
-            a.col = (const int*)(d_pat + rpb);
-            a.val = (const double*)d_sys;
-            a.rhs = (const double*)(d_sys + vb);
-            a.x = d_x;
-            a.res = d_res;
-            a.r = d_work;
-            a.t = d_work + mw;
-            a.inv = d_work + 2 * mw;
-            a.p = in_lds ? nullptr : d_work + 3 * mw;
-            a.tol2 = tol2;
-            a.n = num_nodes;
-            a.max_iterations = cap;
-            const int mode = 5 * sizeof(double) * m <= kPgLdsMax ? 2 : in_lds ? 1 : 0;
-            const size_t lds = mode == 2 ? 5 * sizeof(double) * m : mode == 1 ? sizeof(double) * m : 0;
-            auto launch = [&](auto kernel) {
-                if (lds > 64 * 1024) {   // dynamic LDS beyond the 64 KiB default has to be announced
-                    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    (void)hipGetLastError();
-                }
-                hipLaunchKernelGGL(kernel, dim3(1), dim3(kPgThreads), lds, ctx->stream, a);
-            };
-            if (mode == 2)
-                launch(k_pgcg<2>);
-            else if (mode == 1)
-                launch(k_pgcg<1>);
-            else
-                launch(k_pgcg<0>);
-            LGS_HIP_CHECK(hipGetLastError());
-        } else {
-            PgGridArgs a;
-            a.rowptr = (const int*)d_pat;
-            a.col = (const int*)(d_pat + rpb);
-            a.val = (const double*)d_sys;
-            a.rhs = (const double*)(d_sys + vb);
-            a.x = d_x;
-            a.res = d_res;
-            a.r = d_work;
-            a.z = d_work + mw;
-            a.inv = d_work + 2 * mw;
-            a.t = d_work + 3 * mw;
-            a.p[0] = d_work + 4 * mw;
-            a.p[1] = d_work + 5 * mw;
-            double* const parts = d_work + 6 * mw;
-            a.part_pt = parts;
-            a.part_rr[0] = parts + gw;
-            a.part_rr[1] = parts + 2 * gw;
-            a.part_rz[0] = parts + 3 * gw;
-            a.part_rz[1] = parts + 4 * gw;
-            a.tol2 = tol2;
-            a.n = num_nodes;
-            a.G = G;
-            for (hipEvent_t& e : ctx->pg_ev)
-                if (!e) LGS_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            LGS_HIP_CHECK(hipMemsetAsync(d_res, 0, sizeof(PgResult), ctx->stream));
-            hipLaunchKernelGGL(k_pgcg_grid_init, dim3(G), dim3(kPgGridThreads), 0, ctx->stream, a);
-            LGS_HIP_CHECK(hipGetLastError());
-            // chunks of passes; the record of chunk k is looked at once chunk k + 1 is enqueued
-            PgResult* const seen = (PgResult*)(back + mb + 256);
-            int it = 0;
-            for (int chunk = 0;; ++chunk) {
-                const int end = (int)std::min<long long>((long long)it + kPgGridChunk, cap);
-                for (; it < end; ++it) {
-                    hipLaunchKernelGGL(k_pgcg_grid_spmv, dim3(G), dim3(kPgGridThreads), 0, ctx->stream, a, it, cap);
-                    hipLaunchKernelGGL(k_pgcg_grid_update, dim3(G), dim3(kPgGridThreads), 0, ctx->stream, a, it);
-                }
-                if (it == cap)   // concludes the last pass
-                    hipLaunchKernelGGL(k_pgcg_grid_spmv, dim3(G), dim3(kPgGridThreads), 0, ctx->stream, a, cap, cap);
-                LGS_HIP_CHECK(hipGetLastError());
-                if (it == cap) break;
-                LGS_HIP_CHECK(hipMemcpyAsync(seen + (chunk & 1), d_res, sizeof(PgResult), hipMemcpyDeviceToHost,
-                                             ctx->stream));
-                LGS_HIP_CHECK(hipEventRecord(ctx->pg_ev[chunk & 1], ctx->stream));
-                if (chunk > 0) {
-                    ctx->wait_event(ctx->pg_ev[(chunk - 1) & 1]);
-                    if (seen[(chunk - 1) & 1].done) break;
-                }
-            }
-        }
-        LGS_HIP_CHECK(hipMemcpyAsync(back, d_x, mb + 256, hipMemcpyDeviceToHost, ctx->stream));
+        PgDeviceSystem sys;
+        sys.rowptr = (const int*)d_pat;
+        sys.col = (const int*)(d_pat + rpb);
+        sys.val = (const double*)d_sys;
+        sys.rhs = (const double*)(d_sys + vb);
+        sys.x = (double*)(d_sys + vb + mb);
+        sys.res = (PgResult*)(d_sys + vb + 2 * mb);
+        sys.work = (double*)(d_sys + vb + 2 * mb + 256);
+        sys.seen = (PgResult*)(back + mb + 256);
+        sys.n = num_nodes;
+        const bool grid = pg_solve_enqueue(ctx, sys, tolerance, max_iterations);
+        LGS_HIP_CHECK(hipMemcpyAsync(back, sys.x, mb + 256, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
         ctx->pg_cache = cache;   // the device holds this pattern now
         PgResult res;

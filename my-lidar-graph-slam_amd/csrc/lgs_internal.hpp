@@ -90,6 +90,7 @@ enum Slot {
     S_GS0, S_GS1,   // grid search (k_gs.hip): trig / index tables; partials, results, error word
     S_HC0, S_HC1,   // hill climbing (k_hc.hip, k_hc_sq.hip): global term rows; records, trace, error word
     S_PG0, S_PG1,   // pose-graph CG (k_pgcg.hip): the block pattern; values, right-hand side, vectors, result
+    S_PG2, S_PG3,   // resident pose-graph LM (k_pglm.hip): incidence lists and edges; poses, loss terms, step record
     // bank 1 of the per-batch buffers: a batched call keeps two 64-query
     // chunks in flight (the next chunk's launches go out before the host
     // finishes the previous one), each in its own bank (lgs_ctx::banked)
@@ -432,6 +433,8 @@ struct lgs_ctx {
     long long pg_solves = 0, pg_iterations = 0, pg_patterns = 0, pg_grid_solves = 0;
     int pg_grid_nodes = 1280;    // graphs from this many nodes on solve over many workgroups (LGS_OPT_PGCG_GRID_NODES)
     hipEvent_t pg_ev[2] = {};    // the multi-workgroup solve's chunk records
+    // lgs_pg_lm_optimize (k_pglm.hip): the counters of lgs_pg_lm_stats
+    long long pglm_optimizes = 0, pglm_steps = 0, pglm_pose_uploads = 0, pglm_pose_downloads = 0, pglm_incidence_builds = 0;
     // padded phase-plane buffer (per bank): margins zeroed once per (buffer, layout, set count)
     void* planes_ptr[2] = {};
     int planes_sets[2] = {};
@@ -863,6 +866,35 @@ int guarded(lgs_ctx* ctx, F&& f)
 // including the caller; at most ceil(n / grain) of them).  f must not throw.
 // One parallel region runs at a time; nested calls run inline.
 void host_parallel_for(int n, int grain, const std::function<void(int)>& f);
+
+// The device side of lgs_pg_cg_solve (k_pgcg.hip) over buffers that already
+// sit on the device: what lgs_pg_cg_solve runs after its upload and what the
+// resident LM loop (k_pglm.hip) runs on the system its own kernel wrote.
+struct PgResult {
+    double residual_norm2;
+    double threshold;      // k_pgcg_grid_*: max(tol^2 |rhs|^2, DBL_MIN), kept from pass 0
+    int iterations;
+    int done;              // k_pgcg_grid_*: the solve has ended, later launches return at once
+};
+struct PgDeviceSystem {
+    const int* rowptr;     // [n + 1]
+    const int* col;        // [blocks]
+    const double* val;     // [blocks][9]
+    const double* rhs;     // [3n]
+    double* x;             // [3n] the result
+    PgResult* res;
+    double* work;          // pg_work_bytes(ctx, n)
+    PgResult* seen;        // pinned, two records: the many-workgroup solve's looks at `done`
+    int n;
+};
+inline size_t pg_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+bool pg_runs_grid(const lgs_ctx* ctx, int num_nodes);
+size_t pg_work_bytes(const lgs_ctx* ctx, int num_nodes);
+// enqueues the solve on ctx->stream (tolerance 0: DBL_EPSILON, max_iterations
+// 0: 2 * 3n); the many-workgroup variant waits for its chunks' records, the
+// one-workgroup variant does not wait at all.  x and *res are valid once the
+// stream has run.  True when the solve ran over many workgroups
+bool pg_solve_enqueue(lgs_ctx* ctx, const PgDeviceSystem& s, double tolerance, int max_iterations);
 
 // K3 sort (k_sort.hip): stable LSD radix sort of n 32-bit keys on bits
 // [lo, lo + bits) into `out`; `tmp` (n keys) is used when the sort takes two

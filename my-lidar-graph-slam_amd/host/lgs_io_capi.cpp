@@ -1,5 +1,6 @@
 // lgs_io_capi.cpp -- extern "C" entry points of include/lgs_io.h over the
 // C++ classes of lgs_io.hpp / lgs_posegraph.hpp.  No exception crosses the ABI.
+#include <cstddef>
 #include <cstring>
 #include <sstream>
 
@@ -120,9 +121,20 @@ extern "C" long long lgs_carmen_load(const char* text, double* out, long long ca
 
 namespace {
 
+// the device's edge record is the host's
+static_assert(sizeof(lgs_pg_edge) == sizeof(lgs_pose_graph_edge) &&
+                  offsetof(lgs_pg_edge, start_node_index) == offsetof(lgs_pose_graph_edge, start_node_index) &&
+                  offsetof(lgs_pg_edge, end_node_index) == offsetof(lgs_pose_graph_edge, end_node_index) &&
+                  offsetof(lgs_pg_edge, relative_pose) == offsetof(lgs_pose_graph_edge, relative_pose) &&
+                  offsetof(lgs_pg_edge, information) == offsetof(lgs_pose_graph_edge, information),
+              "lgs_pg_edge has the layout of lgs_pose_graph_edge");
+
+using DevicePath = Mapping::PoseGraphOptimizerLM::DevicePath;
+
 // Optimize over the C arrays; dev null: both solvers on the host
 int optimize_lm(const DevicePtr& dev, lgs_pose_graph_lm_params* p, lgs_pose2d* poses, int n,
-                const lgs_pose_graph_edge* edges, int m, int* iterations, double* total_error)
+                const lgs_pose_graph_edge* edges, int m, int* iterations, double* total_error,
+                DevicePath path = DevicePath::SolveOnly)
 {
     if (!p || n < 0 || m < 0 || (n > 0 && !poses) || (m > 0 && !edges) || p->num_iterations_max < 0)
         return LGS_ERR_INVALID_ARG;
@@ -134,7 +146,8 @@ int optimize_lm(const DevicePtr& dev, lgs_pose_graph_lm_params* p, lgs_pose2d* p
                                 ? Mapping::PoseGraphOptimizerLM::SolverType::SparseCholesky
                                 : Mapping::PoseGraphOptimizerLM::SolverType::ConjugateGradient;
         Mapping::PoseGraphOptimizerLM opt =
-            dev ? Mapping::PoseGraphOptimizerLM(dev, solver, p->num_iterations_max, p->error_tolerance, p->lambda, loss)
+            dev ? Mapping::PoseGraphOptimizerLM(dev, solver, p->num_iterations_max, p->error_tolerance, p->lambda, loss,
+                                                path)
                 : Mapping::PoseGraphOptimizerLM(solver, p->num_iterations_max, p->error_tolerance, p->lambda, loss);
         std::vector<Mapping::PoseGraph::Node> nodes;
         nodes.reserve((size_t)n);
@@ -167,6 +180,45 @@ extern "C" int lgs_pose_graph_optimize_lm_device(lgs_ctx* ctx, lgs_pose_graph_lm
 {
     if (!ctx) return LGS_ERR_INVALID_ARG;
     return optimize_lm(std::make_shared<Device>(ctx), p, poses, n, edges, m, iterations, total_error);
+}
+
+extern "C" int lgs_pose_graph_optimize_lm_resident(lgs_ctx* ctx, lgs_pose_graph_lm_params* p, lgs_pose2d* poses, int n,
+                                                   const lgs_pose_graph_edge* edges, int m, int* iterations,
+                                                   double* total_error)
+{
+    if (!ctx || !p || p->solver != LGS_LM_CONJUGATE_GRADIENT) return LGS_ERR_INVALID_ARG;
+    return optimize_lm(std::make_shared<Device>(ctx), p, poses, n, edges, m, iterations, total_error,
+                       DevicePath::Resident);
+}
+
+extern "C" int lgs_pose_graph_linearize(const lgs_pose_graph_lm_params* p, const lgs_pose2d* poses, int n,
+                                        const lgs_pose_graph_edge* edges, int m, double* diag, int* num_pairs,
+                                        int* pairs, double* off, double* rhs)
+{
+    if (!p || n < 1 || m < 0 || !poses || !diag || !num_pairs || !rhs || (m > 0 && (!edges || !pairs || !off)))
+        return LGS_ERR_INVALID_ARG;
+    return guarded([&] {
+        auto loss = Mapping::CreateLossFunction(p->loss_kind, p->loss_scale);
+        if (!loss) return LGS_ERR_INVALID_ARG;
+        const Mapping::PoseGraphOptimizerLM opt(Mapping::PoseGraphOptimizerLM::SolverType::ConjugateGradient, 1, 0.0,
+                                                p->lambda, loss);
+        std::vector<Mapping::PoseGraph::Node> nodes;
+        nodes.reserve((size_t)n);
+        for (int i = 0; i < n; ++i) nodes.emplace_back(i, RobotPose2D<double>(poses[i].x, poses[i].y, poses[i].theta));
+        std::vector<std::array<double, 9>> d, o;
+        std::vector<std::pair<int, int>> pr;
+        std::vector<double> r;
+        opt.Linearize(nodes, to_edges(edges, m), d, pr, o, r);
+        std::memcpy(diag, d.data(), sizeof(double) * 9 * d.size());
+        std::memcpy(rhs, r.data(), sizeof(double) * r.size());
+        *num_pairs = (int)pr.size();
+        for (size_t k = 0; k < pr.size(); ++k) {
+            pairs[2 * k] = pr[k].first;
+            pairs[2 * k + 1] = pr[k].second;
+            std::memcpy(off + 9 * k, o[k].data(), sizeof(double) * 9);
+        }
+        return LGS_OK;
+    });
 }
 
 extern "C" int lgs_robust_loss(int kind, double scale, const double* t, int n, double* out)

@@ -460,11 +460,17 @@ double PoseGraphOptimizerLM::ComputeTotalError(const std::vector<PoseGraph::Node
     return total;
 }
 
-void PoseGraphOptimizerLM::OptimizeStep(std::vector<PoseGraph::Node>& nodes,
-                                        const std::vector<PoseGraph::Edge>& edges)
+// :84-172: H and b from every edge, the 1e9 anchor on node 0, lambda on the
+// diagonal; rhs = -b.  The one copy of the linearisation: OptimizeStep solves
+// this system and Linearize hands it out (the device's k_pg_linearise is
+// checked against it byte for byte).
+namespace {
+
+void linearise(const PoseGraphOptimizerLM& opt, const LossFunction& loss, double lambda,
+               const std::vector<PoseGraph::Node>& nodes, const std::vector<PoseGraph::Edge>& edges, BlockMatrix& H,
+               std::vector<double>& rhs)
 {
     const int n = (int)nodes.size();
-    BlockMatrix H;
     H.reset(n);
     std::vector<double> b((size_t)3 * n, 0.0);
     for (const auto& edge : edges) {
@@ -479,9 +485,9 @@ void PoseGraphOptimizerLM::OptimizeStep(std::vector<PoseGraph::Node>& nodes,
         const Mat3 Js{ -cosT, -sinT, ex, sinT, -cosT, ey, 0.0, 0.0, -1.0 };
         const Mat3 Je{ cosT, sinT, 0.0, -sinT, cosT, 0.0, 0.0, 0.0, 1.0 };
         Vec3 e;
-        ComputeErrorFunction(sp, ep, edge.RelativePose(), e);
+        opt.ComputeErrorFunction(sp, ep, edge.RelativePose(), e);
         // robust weight of e^T Lambda e (:113-115)
-        const double w = mLossFunction->Weight(quad(e, edge.InformationMatrix()));
+        const double w = loss.Weight(quad(e, edge.InformationMatrix()));
         Mat3 W;
         for (int k = 0; k < 9; ++k) W[k] = w * edge.InformationMatrix().m[k];
         const Mat3 JsW = mul_tn(Js, W), JeW = mul_tn(Je, W);
@@ -508,9 +514,35 @@ void PoseGraphOptimizerLM::OptimizeStep(std::vector<PoseGraph::Node>& nodes,
     if (n > 0)
         for (int k = 0; k < 3; ++k) H.diag[0][4 * k] += 1e9;
     for (int v = 0; v < n; ++v)
-        for (int k = 0; k < 3; ++k) H.diag[v][4 * k] += mLambda;
-    std::vector<double> rhs(b.size());
+        for (int k = 0; k < 3; ++k) H.diag[v][4 * k] += lambda;
+    rhs.resize(b.size());
     for (size_t i = 0; i < b.size(); ++i) rhs[i] = -b[i];
+}
+}  // namespace
+
+void PoseGraphOptimizerLM::Linearize(const std::vector<PoseGraph::Node>& nodes,
+                                     const std::vector<PoseGraph::Edge>& edges, std::vector<std::array<double, 9>>& diag,
+                                     std::vector<std::pair<int, int>>& pairs, std::vector<std::array<double, 9>>& off,
+                                     std::vector<double>& rhs) const
+{
+    for (const auto& edge : edges)
+        if (edge.StartNodeIndex() < 0 || edge.StartNodeIndex() >= (int)nodes.size() || edge.EndNodeIndex() < 0 ||
+            edge.EndNodeIndex() >= (int)nodes.size())
+            throw std::out_of_range("PoseGraphOptimizerLM: edge node index out of range");
+    BlockMatrix H;
+    linearise(*this, *mLossFunction, mLambda, nodes, edges, H, rhs);
+    diag = std::move(H.diag);
+    pairs = std::move(H.pairs);
+    off = std::move(H.off);
+}
+
+void PoseGraphOptimizerLM::OptimizeStep(std::vector<PoseGraph::Node>& nodes,
+                                        const std::vector<PoseGraph::Edge>& edges)
+{
+    const int n = (int)nodes.size();
+    BlockMatrix H;
+    std::vector<double> rhs;
+    linearise(*this, *mLossFunction, mLambda, nodes, edges, H, rhs);
     std::vector<double> delta;
     if (mSolverType == SolverType::SparseCholesky) {
         delta = solve_cholesky(H, rhs);
@@ -545,6 +577,10 @@ void PoseGraphOptimizerLM::Optimize(std::vector<PoseGraph::Node>& nodes, const s
         if (edge.StartNodeIndex() < 0 || edge.StartNodeIndex() >= (int)nodes.size() || edge.EndNodeIndex() < 0 ||
             edge.EndNodeIndex() >= (int)nodes.size())
             throw std::out_of_range("PoseGraphOptimizerLM: edge node index out of range");   // the reference's .at()
+    if (mDev && mPath == DevicePath::Resident) {
+        OptimizeResident(nodes, edges);
+        return;
+    }
     double prevTotalError = std::numeric_limits<double>::max();
     double totalError = std::numeric_limits<double>::max();
     int numOfIterations = 0;
@@ -562,6 +598,55 @@ void PoseGraphOptimizerLM::Optimize(std::vector<PoseGraph::Node>& nodes, const s
     }
     mLastIterations = numOfIterations;
     mLastTotalError = totalError;
+}
+
+PoseGraphOptimizerLM::PoseGraphOptimizerLM(DevicePtr dev, SolverType solverType, int numOfIterationsMax,
+                                           double errorTolerance, double initialLambda, LossFunctionPtr lossFunction,
+                                           DevicePath path)
+    : mSolverType(solverType), mNumOfIterationsMax(numOfIterationsMax), mErrorTolerance(errorTolerance),
+      mLambda(initialLambda), mLossFunction(std::move(lossFunction)), mDev(std::move(dev)), mPath(path)
+{
+    if (mDev && mPath == DevicePath::Resident) {
+        if (mSolverType != SolverType::ConjugateGradient)
+            throw Error(LGS_ERR_INVALID_ARG, "PoseGraphOptimizerLM: the sparse Cholesky solver runs on the host only");
+        if (!mLossFunction || mLossFunction->Kind() < 0)
+            throw Error(LGS_ERR_INVALID_ARG, "PoseGraphOptimizerLM: the device evaluates the built-in losses only");
+    }
+}
+
+// Optimize with the graph resident on the device: the loop of Optimize runs
+// inside lgs_pg_lm_optimize, with the damping factor in and out
+void PoseGraphOptimizerLM::OptimizeResident(std::vector<PoseGraph::Node>& nodes,
+                                            const std::vector<PoseGraph::Edge>& edges)
+{
+    std::vector<lgs_pose2d> poses(nodes.size());
+    for (size_t i = 0; i < nodes.size(); ++i) poses[i] = { nodes[i].Pose().mX, nodes[i].Pose().mY, nodes[i].Pose().mTheta };
+    std::vector<lgs_pg_edge> flat(edges.size());
+    for (size_t i = 0; i < edges.size(); ++i) {
+        flat[i].start_node_index = edges[i].StartNodeIndex();
+        flat[i].end_node_index = edges[i].EndNodeIndex();
+        flat[i].relative_pose = { edges[i].RelativePose().mX, edges[i].RelativePose().mY, edges[i].RelativePose().mTheta };
+        for (int k = 0; k < 9; ++k) flat[i].information[k] = edges[i].InformationMatrix().m[k];
+    }
+    lgs_pg_lm_params params;
+    params.num_iterations_max = mNumOfIterationsMax;
+    params.error_tolerance = mErrorTolerance;
+    params.loss_kind = mLossFunction->Kind();
+    params.loss_scale = mLossFunction->Scale();
+    double lambda = mLambda, totalError = 0.0;
+    int iterations = 0;
+    long long passes = 0;
+    mLastSolverIterations = 0;
+    mDev->Check(lgs_pg_lm_optimize(mDev->Handle(), &params, &lambda, poses.empty() ? nullptr : poses.data(),
+                                   (int)poses.size(), flat.empty() ? nullptr : flat.data(), (int)flat.size(), &iterations,
+                                   &totalError, &passes),
+                "lgs_pg_lm_optimize");
+    for (size_t i = 0; i < nodes.size(); ++i)
+        nodes[i].Pose() = RobotPose2D<double>(poses[i].x, poses[i].y, poses[i].theta);
+    mLambda = lambda;
+    mLastIterations = iterations;
+    mLastTotalError = totalError;
+    mLastSolverIterations = passes;
 }
 
 }  // namespace Mapping

@@ -19,12 +19,21 @@
 // with a Device runs that recurrence on the GPU instead (lgs_pg_cg_solve,
 // DESIGN.md §4.7b): thousands of strictly sequential passes over a sparse
 // matrix-vector product, which one workgroup walks far faster than a host
-// core.  No Eigen: matrices are row-major std::array.
+// core.  With DevicePath::Resident the whole Optimize stays on the device
+// (lgs_pg_lm_optimize): poses and edges go up once, every
+// step's linearisation, solve, pose update and per-edge loss run there, and
+// the poses come down once.  Its system is the host linearisation's byte for
+// byte (all losses but Welsch), so it takes the SolveOnly path's steps.
+// Measured (DESIGN.md §8, 1000 to 20000 nodes) it is the faster of the two at
+// every size, by 1-3 % of a step, since the CG passes are nearly all of a
+// step: prefer it wherever the loss is built in.
+// No Eigen: matrices are row-major std::array.
 #pragma once
 
 #include <array>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lgs_slam_hip.hpp"
@@ -99,6 +108,11 @@ public:
     virtual ~LossFunction() = default;
     virtual double Loss(double squaredError) const = 0;
     virtual double Weight(double squaredError) const = 0;
+    // which of the built-in losses this is (the kinds of CreateLossFunction)
+    // and its scale: what a device-resident optimizer evaluates in place of
+    // the virtual calls.  -1: a loss of the caller's own, host only
+    virtual int Kind() const { return -1; }
+    virtual double Scale() const { return 1.0; }
 };
 using LossFunctionPtr = std::shared_ptr<LossFunction>;
 
@@ -106,24 +120,27 @@ class LossSquared final : public LossFunction {   // H/mapping/robust_loss_funct
 public:
     double Loss(double t) const override { return t; }
     double Weight(double) const override { return 1.0; }
+    int Kind() const override { return 6; }
 };
 
-#define LGS_SCALED_LOSS(Name)                                   \
+#define LGS_SCALED_LOSS(Name, KindValue)                        \
     class Name final : public LossFunction {                    \
     public:                                                     \
         explicit Name(double scale) : mScale(scale) {}          \
         double Loss(double squaredError) const override;        \
         double Weight(double squaredError) const override;      \
+        int Kind() const override { return KindValue; }         \
+        double Scale() const override { return mScale; }        \
                                                                 \
     private:                                                    \
         double mScale;                                          \
     };
-LGS_SCALED_LOSS(LossHuber)          // :17-43
-LGS_SCALED_LOSS(LossCauchy)         // :45-72
-LGS_SCALED_LOSS(LossFair)           // :74-103
-LGS_SCALED_LOSS(LossGemanMcClure)   // :105-134
-LGS_SCALED_LOSS(LossWelsch)         // :136-162
-LGS_SCALED_LOSS(LossDCS)            // :164-188
+LGS_SCALED_LOSS(LossHuber, 0)          // :17-43
+LGS_SCALED_LOSS(LossCauchy, 1)         // :45-72
+LGS_SCALED_LOSS(LossFair, 2)           // :74-103
+LGS_SCALED_LOSS(LossGemanMcClure, 3)   // :105-134
+LGS_SCALED_LOSS(LossWelsch, 4)         // :136-162
+LGS_SCALED_LOSS(LossDCS, 5)            // :164-188
 #undef LGS_SCALED_LOSS
 
 // kind: 0 Huber, 1 Cauchy, 2 Fair, 3 GemanMcClure, 4 Welsch, 5 DCS, 6 Squared
@@ -133,6 +150,10 @@ LossFunctionPtr CreateLossFunction(int kind, double scale);
 class PoseGraphOptimizerLM final {
 public:
     enum class SolverType { SparseCholesky, ConjugateGradient };
+    // what an optimizer constructed with a Device runs there: the
+    // ConjugateGradient solve of every step (the rest on the host), or the
+    // whole Optimize
+    enum class DevicePath { SolveOnly, Resident };
 
     PoseGraphOptimizerLM(SolverType solverType, int numOfIterationsMax, double errorTolerance, double initialLambda,
                          LossFunctionPtr lossFunction)
@@ -143,10 +164,12 @@ public:
     // order, so poses agree with the host solve to rounding, not bitwise).
     // The linearisation, the pose update and the error stay on the host, and
     // SolverType::SparseCholesky behaves exactly as without a device.
+    // DevicePath::Resident keeps the pose graph on the device across the
+    // steps of an Optimize (lgs_pg_lm_optimize); it throws Error for
+    // SolverType::SparseCholesky and for a loss whose Kind() is -1, which
+    // exist on the host only, and Optimize then needs at least one node.
     PoseGraphOptimizerLM(DevicePtr dev, SolverType solverType, int numOfIterationsMax, double errorTolerance,
-                         double initialLambda, LossFunctionPtr lossFunction)
-        : mSolverType(solverType), mNumOfIterationsMax(numOfIterationsMax), mErrorTolerance(errorTolerance),
-          mLambda(initialLambda), mLossFunction(std::move(lossFunction)), mDev(std::move(dev)) {}
+                         double initialLambda, LossFunctionPtr lossFunction, DevicePath path = DevicePath::SolveOnly);
 
     // C/mapping/pose_graph_optimizer_lm.cpp:13-65.  The damping factor is a
     // member and carries over to the next call, as in the reference.
@@ -164,6 +187,14 @@ public:
     // CG passes of the device solves of the last Optimize, all steps together (0 without a device)
     long long LastSolverIterations() const { return mLastSolverIterations; }
 
+    // H and the right-hand side of one step at the given poses, on the host:
+    // one diagonal block per node, one block (a, b), a < b, per connected node
+    // pair in the order the edges first name it, rhs = -b.  What OptimizeStep
+    // solves (it calls the same code).
+    void Linearize(const std::vector<PoseGraph::Node>& poseGraphNodes, const std::vector<PoseGraph::Edge>& poseGraphEdges,
+                   std::vector<std::array<double, 9>>& diag, std::vector<std::pair<int, int>>& pairs,
+                   std::vector<std::array<double, 9>>& off, std::vector<double>& rhs) const;
+
 private:
     // :68-220: H and b from every edge, the 1e9 anchor on node 0, lambda on the
     // diagonal, then H delta = -b; poses += delta
@@ -177,6 +208,8 @@ private:
     int mLastIterations = 0;
     double mLastTotalError = 0.0;
     DevicePtr mDev;   // null: both solvers on the host
+    DevicePath mPath = DevicePath::SolveOnly;
+    void OptimizeResident(std::vector<PoseGraph::Node>& poseGraphNodes, const std::vector<PoseGraph::Edge>& poseGraphEdges);
     long long mLastSolverIterations = 0;
 };
 

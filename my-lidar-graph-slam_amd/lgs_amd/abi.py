@@ -207,6 +207,27 @@ class KernelStat(C.Structure):
 
 # (name, restype, argtypes) for every symbol of include/lgs_hip.h
 _P = C.c_void_p
+class PgEdge(C.Structure):
+    """lgs_pg_edge (the layout of lgs_io.h's lgs_pose_graph_edge)"""
+    _fields_ = [("start_node_index", C.c_int), ("end_node_index", C.c_int), ("relative_pose", Pose2D),
+                ("information", C.c_double * 9)]
+
+
+class PgLmParams(C.Structure):
+    _fields_ = [("num_iterations_max", C.c_int), ("error_tolerance", C.c_double), ("loss_kind", C.c_int),
+                ("loss_scale", C.c_double)]
+
+
+def pg_edges(edges):
+    """edges: [(start, end, (x, y, theta), info 3x3)] -> a PgEdge array"""
+    arr = (PgEdge * max(1, len(edges)))()
+    for k, (s, e, z, info) in enumerate(edges):
+        arr[k].start_node_index, arr[k].end_node_index = s, e
+        arr[k].relative_pose = Pose2D(*z)
+        arr[k].information[:] = [float(v) for v in np.asarray(info, dtype=np.float64).reshape(9)]
+    return arr
+
+
 _PROTOS = [
     ("lgs_abi_version", C.c_int, []),
     ("lgs_ctx_create", C.c_int, [C.c_int, C.POINTER(_P)]),
@@ -332,6 +353,13 @@ _PROTOS = [
                                   C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("lgs_pg_cg_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                   C.POINTER(C.c_longlong)]),
+    ("lgs_pg_lm_optimize", C.c_int, [_P, C.POINTER(PgLmParams), C.POINTER(C.c_double), C.POINTER(Pose2D), C.c_int, _P,
+                                     C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
+    ("lgs_pg_lm_linearize", C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.POINTER(Pose2D), C.c_int, _P, C.c_int,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("lgs_pg_lm_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                  C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("lgs_debug_keysort", C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
     ("lgs_debug_map_rebuilds", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("lgs_debug_copy_counters", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -858,6 +886,46 @@ class Context:
         self.check(self.lib.lgs_pg_cg_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "pg_cg_stats")
         return dict(solves=a.value, iterations=b.value, patterns=c.value, grid_solves=d.value)
 
+    def pg_lm_optimize(self, poses, edges, iters: int = 10, tol: float = 1e-3, lam: float = 1e-4, loss: int = 0,
+                       scale: float = 1.0):
+        """lgs_pg_lm_optimize: PoseGraphOptimizerLM::Optimize with the graph resident on
+        the device.  poses [n, 3]; edges [(start, end, (x, y, theta), info 3x3)] or
+        a pg_edges() array -> (poses [n, 3], LM steps, total error, lambda after, CG passes)"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        n = poses.shape[0]
+        out = poses.copy()
+        earr, m = (edges, len(edges)) if isinstance(edges, C.Array) else (pg_edges(edges), len(edges))
+        prm = PgLmParams(int(iters), float(tol), int(loss), float(scale))
+        lam_io, it, tot, passes = C.c_double(lam), C.c_int(), C.c_double(), C.c_longlong()
+        self.check(self.lib.lgs_pg_lm_optimize(self.h, C.byref(prm), C.byref(lam_io),
+                                               out.ctypes.data_as(C.POINTER(Pose2D)) if n else None, n,
+                                               C.cast(earr, _P) if m else None, m, C.byref(it), C.byref(tot),
+                                               C.byref(passes)), "pg_lm_optimize")
+        return out, it.value, tot.value, lam_io.value, passes.value
+
+    def pg_lm_linearize(self, poses, edges, lam: float = 1e-4, loss: int = 0, scale: float = 1.0):
+        """lgs_pg_lm_linearize: the device's H and right-hand side of one LM step ->
+        (diag [n, 3, 3], pairs [p, 2] in first-appearance order, off [p, 3, 3], rhs [3n])"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        n = poses.shape[0]
+        earr, m = (edges, len(edges)) if isinstance(edges, C.Array) else (pg_edges(edges), len(edges))
+        diag, rhs = np.zeros((max(n, 1), 3, 3)), np.zeros(3 * max(n, 1))
+        pairs, off = np.zeros((max(m, 1), 2), dtype=np.int32), np.zeros((max(m, 1), 3, 3))
+        npairs = C.c_int()
+        self.check(self.lib.lgs_pg_lm_linearize(self.h, int(loss), float(scale), float(lam),
+                                                poses.ctypes.data_as(C.POINTER(Pose2D)) if n else None, n,
+                                                C.cast(earr, _P) if m else None, m, dptr(diag), C.byref(npairs),
+                                                pairs.ctypes.data_as(C.POINTER(C.c_int)), dptr(off), dptr(rhs)),
+                   "pg_lm_linearize")
+        return diag[:n], pairs[:npairs.value].copy(), off[:npairs.value].copy(), rhs[:3 * n]
+
+    def pg_lm_stats(self) -> dict:
+        """lgs_pg_lm_stats: resident Optimize calls, LM steps, pose uploads and downloads, incidence-list builds"""
+        v = [C.c_longlong() for _ in range(5)]
+        self.check(self.lib.lgs_pg_lm_stats(self.h, *[C.byref(x) for x in v]), "pg_lm_stats")
+        return dict(zip(("optimizes", "steps", "pose_uploads", "pose_downloads", "incidence_builds"),
+                        [x.value for x in v]))
+
     def map(self, res: float, patch_size: int, ncx: int, ncy: int, center=(0.0, 0.0)) -> "Map":
         h = _P()
         self.check(self.lib.lgs_map_create(self.h, res, patch_size, ncx, ncy, center[0], center[1],
@@ -904,7 +972,8 @@ class Context:
 
     def debug_libm(self, op: int, x) -> np.ndarray:
         """Diagnostics: the device's glibc sincos (op 0, rows of (sin, cos)) or
-        pow(x, 3.0) (op 1) on the GPU (lgs_debug_libm)."""
+        pow(x, 3.0) (op 1) on the GPU, or the device's sqrt(x) (op 2) and
+        fmod(x, 2 pi) (op 3) (lgs_debug_libm)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         out = np.zeros((len(x), 2) if op == 0 else len(x), dtype=np.float64)
         self.check(self.lib.lgs_debug_libm(self.h, op, x.ctypes.data_as(_P), len(x), out.ctypes.data_as(_P)),

@@ -47,6 +47,10 @@ _PROTOS = [
                                              C.POINTER(PoseGraphEdge), C.c_int, C.POINTER(C.c_int), _D]),
     ("lgs_pose_graph_optimize_lm_device", C.c_int, [_P, C.POINTER(LMParams), C.POINTER(Pose2D), C.c_int,
                                                     C.POINTER(PoseGraphEdge), C.c_int, C.POINTER(C.c_int), _D]),
+    ("lgs_pose_graph_optimize_lm_resident", C.c_int, [_P, C.POINTER(LMParams), C.POINTER(Pose2D), C.c_int,
+                                                      C.POINTER(PoseGraphEdge), C.c_int, C.POINTER(C.c_int), _D]),
+    ("lgs_pose_graph_linearize", C.c_int, [C.POINTER(LMParams), C.POINTER(Pose2D), C.c_int, C.POINTER(PoseGraphEdge),
+                                           C.c_int, _D, C.POINTER(C.c_int), C.POINTER(C.c_int), _D, _D]),
     ("lgs_robust_loss", C.c_int, [C.c_int, C.c_double, _D, C.c_int, _D]),
     ("lgs_map_draw_image", C.c_int, [_P, _P, C.POINTER(Pose2D), C.c_int, C.POINTER(MapSaveOptions),
                                      C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -104,10 +108,12 @@ def edges_array(edges):
 
 
 def optimize_lm(poses, edges, solver=LM_SPARSE_CHOLESKY, iters=10, tol=1e-3, lam=1e-4, loss="huber",
-                scale=1.0, ctx: Optional["abi.Context"] = None):
+                scale=1.0, ctx: Optional["abi.Context"] = None, resident: bool = False):
     """PoseGraphOptimizerLM::Optimize -> (poses [n, 3], iterations, total error, lambda after).
     With a context the ConjugateGradient solve of every step runs on its device
-    (lgs_pose_graph_optimize_lm_device); edges may be an edges_array() result."""
+    (lgs_pose_graph_optimize_lm_device), with resident=True every step does and
+    the graph stays there (lgs_pose_graph_optimize_lm_resident); edges may be an
+    edges_array() result."""
     L = load()
     n = len(poses)
     p = (Pose2D * max(1, n))(*[Pose2D(*q) for q in poses])
@@ -117,13 +123,35 @@ def optimize_lm(poses, edges, solver=LM_SPARSE_CHOLESKY, iters=10, tol=1e-3, lam
         earr, m = edges, len(edges)
     else:
         earr, m = edges_array(edges), len(edges)
+    if resident and ctx is None:
+        raise ValueError("resident=True needs a context")
     if ctx is None:
         rc = L.lgs_pose_graph_optimize_lm(C.byref(prm), p, n, earr, m, C.byref(it), C.byref(tot))
+    elif resident:
+        rc = L.lgs_pose_graph_optimize_lm_resident(ctx.h, C.byref(prm), p, n, earr, m, C.byref(it), C.byref(tot))
     else:
         rc = L.lgs_pose_graph_optimize_lm_device(ctx.h, C.byref(prm), p, n, earr, m, C.byref(it), C.byref(tot))
     if rc != 0:
-        raise RuntimeError(f"lgs_pose_graph_optimize_lm{'' if ctx is None else '_device'}: status {rc}")
+        which = "" if ctx is None else "_resident" if resident else "_device"
+        raise RuntimeError(f"lgs_pose_graph_optimize_lm{which}: status {rc}")
     return np.array([[q.x, q.y, q.theta] for q in p[:n]]), it.value, tot.value, prm.lambda_
+
+
+def linearize(poses, edges, lam=1e-4, loss="huber", scale=1.0):
+    """lgs_pose_graph_linearize: the host's H and right-hand side of one LM step ->
+    (diag [n, 3, 3], pairs [p, 2] in first-appearance order, off [p, 3, 3], rhs [3n])"""
+    n = len(poses)
+    p = (Pose2D * max(1, n))(*[Pose2D(*q) for q in poses])
+    prm = LMParams(LM_CONJUGATE_GRADIENT, 1, 0.0, lam, LOSSES[loss] if isinstance(loss, str) else loss, scale)
+    earr, m = (edges, len(edges)) if isinstance(edges, C.Array) else (edges_array(edges), len(edges))
+    diag, rhs = np.zeros((max(n, 1), 3, 3)), np.zeros(3 * max(n, 1))
+    pairs, off = np.zeros((max(m, 1), 2), dtype=np.int32), np.zeros((max(m, 1), 3, 3))
+    npairs = C.c_int()
+    rc = load().lgs_pose_graph_linearize(C.byref(prm), p, n, earr, m, _dp(diag), C.byref(npairs),
+                                         pairs.ctypes.data_as(C.POINTER(C.c_int)), _dp(off), _dp(rhs))
+    if rc != 0:
+        raise RuntimeError(f"lgs_pose_graph_linearize: status {rc}")
+    return diag[:n], pairs[:npairs.value].copy(), off[:npairs.value].copy(), rhs[:3 * n]
 
 
 def robust_loss(kind, scale, t):

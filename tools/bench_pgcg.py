@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The pose graph's Levenberg-Marquardt step with its three linear solvers: the
 host's conjugate gradients and sparse Cholesky (PoseGraphOptimizerLM as it was)
-and the conjugate gradients on the device (lgs_pg_cg_solve, k_pgcg.hip), on
+and the conjugate gradients on the device (lgs_pg_cg_solve, k_pgcg.hip), and
+the whole step on the device (lgs_pg_lm_optimize, k_pglm.hip), on
 tests/lm_oracle.random_graph at 1000 nodes / 40 loop edges, 5000 / 200 and
 20000 / 1000 (Huber loss, lambda 1e-4, the launcher's tolerance-free steps:
 every call runs the LM steps it is asked for).
@@ -10,6 +11,16 @@ Prints one JSON line per graph size and appends it to --out:
   host_cg_ms_per_step, host_cholesky_ms_per_step, device_cg_ms_per_step
         wall clock of an Optimize of --steps LM steps, per step (linearisation,
         solve, pose update, total error); the device call after a warm-up call
+  resident_ms_per_step    the same Optimize with the graph resident on the device
+        (lgs_pg_lm_optimize, k_pglm.hip: linearisation, solve, pose update and
+        loss on the device), timed in the same run as device_cg_ms_per_step, the
+        two calls alternating, the fastest of --repeat each
+  resident_abi_ms_per_step   lgs_pg_lm_optimize called on arrays that are already
+        flat (no per-call conversion of poses and edges, which both
+        io.optimize_lm figures above pay alike)
+  device_cg_runs_ms, resident_runs_ms   every timed call, per step (the spread)
+  device_cg_remainder_ms, resident_remainder_ms   per step: the step time minus
+        cg_passes_per_step x us_per_cg_pass of the variant the library picks
   cg_passes_per_step      CG passes the device solves ran, per LM step
   variant                 which of the two device solves the library picks at
                           this size: one persistent workgroup, or many
@@ -105,11 +116,24 @@ def gpu_step(args):
         host_cg_steps = max(1, min(k, 2 if n >= 5000 else k))
         t_cg, _ = timed(lambda: opt(io.LM_CONJUGATE_GRADIENT, host_cg_steps), 1)
         t_ch, ref = timed(lambda: opt(io.LM_SPARSE_CHOLESKY, k), 2)
+        res = lambda steps: io.optimize_lm(init, earr, solver=io.LM_CONJUGATE_GRADIENT, iters=steps, ctx=ctx,
+                                           resident=True, **LM)
         opt(io.LM_CONJUGATE_GRADIENT, 1, ctx)   # warm-up: code object, arena, pinned staging
+        res(1)
         before = ctx.pg_cg_stats()
-        t_dev, out = timed(lambda: opt(io.LM_CONJUGATE_GRADIENT, k, ctx), args.repeat)
+        dev_runs, res_runs, abi_runs = [], [], []
+        parr = abi.pg_edges(edges)
+        for _ in range(args.repeat):             # the two paths alternate
+            t, out = timed(lambda: opt(io.LM_CONJUGATE_GRADIENT, k, ctx), 1)
+            dev_runs.append(t)
+            t, out_res = timed(lambda: res(k), 1)
+            res_runs.append(t)
+            t, _ = timed(lambda: ctx.pg_lm_optimize(init, parr, iters=k, tol=LM["tol"], lam=LM["lam"], loss=0,
+                                                    scale=LM["scale"]), 1)
+            abi_runs.append(t)
+        t_dev, t_res = min(dev_runs), min(res_runs)
         after = ctx.pg_cg_stats()
-        passes_per_step = (after["iterations"] - before["iterations"]) / float(args.repeat * k)
+        passes_per_step = (after["iterations"] - before["iterations"]) / float(3 * args.repeat * k)
         diag, pairs, off, rhs = first_step_blocks(init, edges, LM["lam"])
         solves = {}
         for how, nodes in (("workgroup", 2 ** 31 - 1), ("grid", 0)):
@@ -121,14 +145,24 @@ def gpu_step(args):
                                one_pass_ms=round(1e3 * t_one, 3),
                                us_per_cg_pass=round(1e6 * (t_full - t_one) / max(1, sol[1] - 1), 3))
         ctx.set_option(abi.LGS_OPT_PGCG_GRID_NODES, GRID_NODES_DEFAULT)
+        picked = "grid" if n >= GRID_NODES_DEFAULT else "workgroup"
+        solve_ms = passes_per_step * solves[picked]["us_per_cg_pass"] * 1e-3
         line = dict(line="pgcg", nodes=n, loop_edges=loops, edges=len(edges), pairs=int(len(pairs)), lm_steps=k,
                     host_cg_ms_per_step=round(1e3 * t_cg / host_cg_steps, 3),
                     host_cholesky_ms_per_step=round(1e3 * t_ch / k, 3),
                     device_cg_ms_per_step=round(1e3 * t_dev / k, 3),
+                    resident_ms_per_step=round(1e3 * t_res / k, 3),
+                    device_cg_runs_ms=[round(1e3 * t / k, 3) for t in dev_runs],
+                    resident_runs_ms=[round(1e3 * t / k, 3) for t in res_runs],
+                    device_cg_remainder_ms=round(1e3 * t_dev / k - solve_ms, 3),
+                    resident_remainder_ms=round(1e3 * t_res / k - solve_ms, 3),
+                    device_over_resident=round(t_dev / t_res, 3),
+                    resident_abi_ms_per_step=round(1e3 * min(abi_runs) / k, 3),
+                    resident_pose_diff_vs_device=float(np.abs(out_res[0] - out[0]).max()),
                     cg_passes_per_step=round(passes_per_step, 1),
                     host_cg_over_device=round((t_cg / host_cg_steps) / (t_dev / k), 2),
                     host_cholesky_over_device=round((t_ch / k) / (t_dev / k), 3),
-                    variant="grid" if n >= GRID_NODES_DEFAULT else "workgroup", solve=solves,
+                    variant=picked, solve=solves,
                     pose_diff_vs_cholesky=float(np.abs(out[0] - ref[0]).max()))
         text = json.dumps(line)
         print(text, flush=True)
