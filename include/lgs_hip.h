@@ -198,7 +198,8 @@ int  lgs_abi_version(void);
 #define LGS_OPT_DEVICE_TIMING 34  /* 1 = while LGS_OPT_PROFILE(_MASK) times a kernel of a correlative batch chunk, time it on the device instead of with stream events: its workgroups stamp s_memrealtime (100 MHz) at start and end into per-chunk words (two relaxed atomic maxima per workgroup), copied back with the chunk's records; a launch's time is its first workgroup's start to its last workgroup's end (the execution span rocprofv3 reports, not the wait of a stream event for the CUs).  Launches outside a chunk's main chain keep event timing.  0 (default) = events */
 #define LGS_OPT_LEAN_PROJECT  35  /* 1 (default) = batched pruned correlative chunks (work list, wide seed, staged fine evaluation) write only the superblock base of every (angle, beam) plus per-beam / per-angle trig tables, and the kernels that stage a coarse-base or cell row form it themselves with the projection's own arithmetic (bit-identical); 0 = every row materialised (the guard fix-up reruns and lone matches always materialise) */
 #define LGS_OPT_PGCG_GRID_NODES 36 /* lgs_pg_cg_solve: systems of at least this many nodes run over many workgroups, two launches per CG pass (default 1280: up to there the vectors of the one-workgroup solve fit LDS and it is the faster one); smaller ones in one persistent workgroup.  0 = always the grid, 2^31 - 1 = never */
-#define LGS_OPT_POISON_WS     15  /* diagnostics: 1 = fill every match workspace and record with 0xFF bytes before the batch runs (any read-before-write shows up) */
+#define LGS_OPT_FAST_ROWS     37  /* 1 (default) = a lean batch's superblock pass forms a wave's 64 hit-point cells with a shorter fp64 chain (csrc/fast_cell.hpp) wherever every lane's cell is certified equal to the exact chain's and unguarded, and with the exact chain otherwise (bit-identical records); 0 = the exact chain always */
+#define LGS_OPT_POISON_WS     15/* diagnostics: 1 = fill every match workspace and record with 0xFF bytes before the batch runs (any read-before-write shows up) */
 int  lgs_ctx_set_option(lgs_ctx* ctx, int option, double value);
 
 /* Diagnostics: copy one intermediate buffer of item `item` of the context's

@@ -28,6 +28,7 @@
 //   k_cost_*    CostGreedyEndpoint::Cost at the best pose and its six
 //               central-difference neighbours (C/mapping/cost_function_greedy_endpoint.cpp:32-171).
 #include "lgs_internal.hpp"
+#include "fast_cell.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -113,6 +114,11 @@ struct MatchItem {
     int inject;              // LGS_OPT_INJECT_INDEX (tests): a guarded projection's x index + 1
     int gcap;                // guard records the record holds (guard_cap)
     double geps;             // the projection guard's epsilon (near_boundary)
+    // certified fast rows (LGS_OPT_FAST_ROWS, fast_cell.hpp): lean_super_row
+    // forms a wave's cells with the fast chain where every lane is certain
+    double fox, foy, fh0;    // lgs_fast::item_consts of this item's pose, map origin and geps
+    float finv_lr;           // 1.0f / low_res (lgs_fast::floor_divmod22)
+    int fast;                // 1: the fast chain may be used (0: today's row code only)
 };
 typedef const MatchItem* __restrict__ Items;
 
@@ -585,24 +591,66 @@ __global__ __launch_bounds__(256) void k_beams(Items items, DevTs dts)
     const int i = s_map[tid];
     double sa, ca;
     sincos(angles[i], &sa, &ca);
-    it.btab[v] = make_double4(ranges[i], ca, sa, 0.0);
+    // fourth lane: r / res for the certified fast rows (NaN: exact chain only)
+    it.btab[v] = make_double4(ranges[i], ca, sa, lgs_fast::beam_rs(ranges[i], 1.0 / pl.res));
+}
+
+// The superblock base of a cell the fast chain certified (lgs_fast::cell):
+// beam_lattice + super_base_l of the octet layout in 32-bit arithmetic.  The
+// lattice coordinates are below 2^22 (fast_cell.hpp), the plane strides below
+// 2^22 (the host sets MatchItem::fast only then) and a base that touches the
+// map below 2^31 (set_plane_layout), so the low 32 bits computed here are the
+// 64-bit expression's value.
+struct FastLattice {
+    int win_x, win_y, lr, Wq, Hq, ncx, ncy, M;
+    unsigned pstrideO4, subO4, Wq44;   // 4 x the strides (the base is unit << 2 | row), each below 2^24
+    float inv_lr;
+};
+__device__ __forceinline__ int fast_super_base(int ix, int iy, const FastLattice& L)
+{
+    int qx0, qy0, rx, ry;
+    lgs_fast::floor_divmod22(ix - L.win_x, L.lr, L.inv_lr, qx0, rx);
+    lgs_fast::floor_divmod22(iy - L.win_y, L.lr, L.inv_lr, qy0, ry);
+    const bool touches = (qx0 < L.Wq) & (qx0 + L.ncx > (rx > 0 ? -1 : 0)) & (qy0 < L.Hq) &
+                         (qy0 + L.ncy > (ry > 0 ? -1 : 0));
+    const unsigned Qx = (unsigned)(qx0 + L.M), Qy = (unsigned)(qy0 + L.M);   // >= 0 when the window touches
+    const unsigned Yr = Qy >> 2;
+    const unsigned u4 = __umul24(__umul24((unsigned)ry, (unsigned)L.lr) + (unsigned)rx, L.pstrideO4) +
+                        __umul24((Qy & 3u) * 4u + (Qx & 3u), L.subO4) + __umul24(Yr >> 2, L.Wq44) + (Qx & ~3u);
+    return touches ? (int)(u4 | (Yr & 3u)) : 0;
 }
 
 // The superblock-base row of angle t into LDS (block-wide), with k_project's
 // guard records (gen-tagged slots of the item's record, the injected index
 // shift of LGS_OPT_INJECT_INDEX) and the angle's edge flag.  Every thread of
 // the block must call it (a barrier inside).
+//
+// Certified fast rows (MatchItem::fast): a wave first forms
+// its 64 cells with the fast chain (lgs_fast::cell); if every lane's cell is
+// certain -- the exact chain would give the same cell and raise no guard --
+// the bases come from it (fast_super_base).  If any lane is uncertain the
+// whole wave runs the exact code below for that iteration, unchanged: guard
+// records, NaN ranges, the injected index and exact boundary hits keep their
+// behaviour by construction.
+// SH: the row entry is the base << SH (k_super_oct's packed gathers).
+template <int SH>
 __device__ __forceinline__ void lean_super_row(const MatchItem& it, int t, int* srow)
 {
     const RtcsmPlan& pl = it.pl;
     RtcsmRecord* rec = it.rec;
     const double inv_res = 1.0 / pl.res, inv_lr = 1.0 / pl.low_res;
     const double2 at = it.atab[t];
+    const bool fast = it.fast != 0;
+    const double fox = it.fox, foy = it.foy, fh0 = it.fh0;
+    const int win_x = pl.win_x, win_y = pl.win_y, Nv = pl.Nv;
+    const FastLattice L = { win_x, win_y, pl.low_res, pl.Wq, pl.Hq, pl.ncx, pl.ncy, pl.M,
+                            (unsigned)pl.pstrideO << 2, (unsigned)pl.subO << 2, (unsigned)pl.Wq4 << 2, it.finv_lr };
     int edge = 0;
-    for (int v = threadIdx.x; v < pl.Nv; v += blockDim.x) {
-        const double4 b = it.btab[v];
-        const double c = at.x * b.y - at.y * b.z;
-        const double s = at.y * b.y + at.x * b.z;
+    // the exact chain of one (angle, beam), k_project's arithmetic; ctca, stca:
+    // its first two products at.x * b.y, at.y * b.y
+    auto exact = [&](int v, const double4& b, double ctca, double stca) {
+        const double c = ctca - at.y * b.z;
+        const double s = stca + at.x * b.z;
         const double hx = pl.sx + b.x * c;
         const double hy = pl.sy + b.x * s;
         const double qx = (hx - pl.min_x) * inv_res;
@@ -622,9 +670,31 @@ __device__ __forceinline__ void lean_super_row(const MatchItem& it, int t, int* 
             }
             ix += it.inject;
         }
-        srow[v] = super_base_l(beam_lattice(ix, iy, pl, inv_lr), pl);
-        LGS_CHK_SUPER(pl, srow[v], t, v);
+        const int sb = super_base_l(beam_lattice(ix, iy, pl, inv_lr), pl);
+        srow[v] = sb << SH;
+        LGS_CHK_SUPER(pl, sb, t, v);
         edge |= (ix - pl.win_x < 0 || iy - pl.win_y < 0) ? 1 : 0;
+    };
+    if (fast) {   // (a loop of its own: the table entry is then one 32-byte read)
+        for (int v = threadIdx.x; v < Nv; v += blockDim.x) {
+            const double4 b = it.btab[v];
+            const double ctca = at.x * b.y, stca = at.y * b.y;   // both chains' first products
+            int fx, fy;
+            const bool certain = lgs_fast::cell(at.x, at.y, b.z, ctca, stca, b.w, fox, foy, fh0, fx, fy);
+            if (!__any(!certain)) {   // wave-uniform
+                const int sb = fast_super_base(fx, fy, L);
+                srow[v] = sb << SH;
+                LGS_CHK_SUPER(pl, sb, t, v);
+                edge |= (fx - win_x < 0 || fy - win_y < 0) ? 1 : 0;
+            } else {
+                exact(v, b, ctca, stca);
+            }
+        }
+    } else {
+        for (int v = threadIdx.x; v < Nv; v += blockDim.x) {
+            const double4 b = it.btab[v];
+            exact(v, b, at.x * b.y, at.y * b.y);
+        }
     }
     // this angle has a beam whose coarse lattice starts left of / below the
     // map: the unsafe-block check runs for it (generation-stamped flag)
@@ -680,7 +750,8 @@ __global__ void k_cost_patch(int4* __restrict__ cidx, const int4* __restrict__ p
 // Copy n elements global -> LDS with the whole workgroup, loads issued in
 // batches of 8 per thread before their stores (a plain strided loop waits one
 // memory latency per element per thread).
-template <class T>
+// SH (int rows): the entries are stored << SH (k_super_oct's packed rows).
+template <class T, int SH = 0>
 __device__ __forceinline__ void stage_lds(T* dst, const T* __restrict__ src, int n)
 {
     const int nt = blockDim.x;
@@ -694,7 +765,11 @@ __device__ __forceinline__ void stage_lds(T* dst, const T* __restrict__ src, int
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int v = v0 + j * nt;
-            if (v < n) dst[v] = x[j];
+            if constexpr (SH != 0) {
+                if (v < n) dst[v] = x[j] << SH;
+            } else {
+                if (v < n) dst[v] = x[j];
+            }
         }
     }
 }
@@ -1442,7 +1517,18 @@ constexpr int kOctRowPad = 64 * (LGS_OCT_PIPE5 > LGS_OCT_PIPE9 ? LGS_OCT_PIPE5 :
 // unit, rows 4q + 8 .. 4q + 11).
 // U8: the unit size in 8-byte words (2: 16-byte units, 3: 24-byte units whose
 // third word holds rows 4q + 8 .. 4q + 11, read with the first two at once)
-template <int NR, int U8>
+// PK (packed gathers, r07): the LDS row entry is the base << 3 = unit << 5 |
+// 8 (first row & 3): its low 5 bits are the window's bit shift inside the unit
+// as v_alignbit / v_lshrrev read it, entry >> 5 the unit.  A gather is the
+// item's uniform unit pointer + a 32-bit byte offset; no per-load select: a
+// beam that misses the map has base 0 (all-zero units), the row's tail is
+// padded with 0 and the idle lanes (q >= nb) read what lane 0 reads (their
+// partials are never summed).  Beams are dealt to the waves interleaved
+// (wave w, step i, slot q: beam (i kSupWaves + w) nb + q), so only the row's
+// global tail needs padding.  The SWAR sums are 32-bit halves (fields never
+// cross bit 32).  The host launches PK only when every unit index fits 27
+// bits (oct_packed_ok), else the unpacked loop.
+template <int NR, int U8, int PK>
 __global__ __launch_bounds__(64 * kSupWaves) void k_super_oct(Items items, const double* __restrict__ zero, DevTs dts)
 {
     static_assert((NR == 5 && U8 == 2) || (NR == 9 && U8 == 3), "8-bit units: 8 rows for 5-row windows, 12 for 9");
@@ -1462,17 +1548,84 @@ __global__ __launch_bounds__(64 * kSupWaves) void k_super_oct(Items items, const
     const int nb = 64 / nsbx;               // beam slots per wave instruction
     const int q = lane / nsbx, a = lane - nsbx * q;
     const bool act = q < nb;
+    constexpr int kOctPipe = oct_pipe<NR>();
     if (it.lean) {   // the row formed here (lean_super_row), k_project does not run
-        lean_super_row(it, t, srow);
+        lean_super_row<PK ? 3 : 0>(it, t, srow);
     } else {
         const int* __restrict__ cbrow = it.cbase + pl.sb_off + (size_t)t * pl.Nv;
-        stage_lds(srow, cbrow, pl.Nv);
+        stage_lds<int, PK ? 3 : 0>(srow, cbrow, pl.Nv);
 #ifdef LGS_CHECK_OFFSETS
-        __syncthreads();
-        for (int v = threadIdx.x; v < pl.Nv; v += blockDim.x) LGS_CHK_SUPER(pl, srow[v], t, v);
+        for (int v = threadIdx.x; v < pl.Nv; v += blockDim.x) LGS_CHK_SUPER(pl, cbrow[v], t, v);
 #endif
     }
+    if constexpr (PK) {
+        // the tail of the interleaved deal: base 0 (oct_row_pad entries on the host)
+        const int pad = kSupWaves * nb * kOctPipe;
+        for (int v = threadIdx.x; v < pad; v += blockDim.x) srow[pl.Nv + v] = 0;
+    }
     __syncthreads();
+    if constexpr (PK) {
+        const unsigned char* __restrict__ ubb = (const unsigned char*)it.super;
+        const int qq = act ? q : 0;                          // idle lanes shadow lane 0
+        const unsigned aoff = act ? (unsigned)a * (4u * U8) : 0u;
+        const int* row = srow + w * nb + qq;                 // step i: row[i kSupWaves nb]
+        const int step = kSupWaves * nb;
+        const int nq = (pl.Nv + step - 1) / step;
+        // exact integer sums of the 8-bit values, SWAR in 32-bit halves of two
+        // 16-bit fields: e0 / o0 window rows (0, 2) / (1, 3), e1 / o1 rows
+        // (4, 6) / (5, 7), r8 the last row (row 4 for NR = 5, row 8 for NR = 9).
+        // A lane sums at most ceil(Nv / (kSupWaves nb)) <= 74 beams (Nv <= 2048
+        // on the pruned path, nb >= 7): <= 74 x 255 < 2^16, no field overflows.
+        constexpr unsigned kM = 0x00FF00FFu;
+        unsigned e0 = 0, o0 = 0, e1 = 0, o1 = 0, r8 = 0;
+        for (int i0 = 0; i0 < nq; i0 += kOctPipe) {
+            unsigned cv[kOctPipe], d0[kOctPipe], d1[kOctPipe], d2[kOctPipe];
+#pragma unroll
+            for (int j = 0; j < kOctPipe; ++j) cv[j] = (unsigned)row[(i0 + j) * step];
+#pragma unroll
+            for (int j = 0; j < kOctPipe; ++j) {
+                const unsigned off = (cv[j] >> 5) * (4u * U8) + aoff;
+                typedef const __attribute__((address_space(1))) unsigned char gbyte_t;
+                gbyte_t* pu = (gbyte_t*)ubb + off;
+                if constexpr (U8 == 2) {   // one 8-byte unit: rows 4q .. 4q + 7
+                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+                    typedef const __attribute__((address_space(1))) u32x2 gu32x2_t;
+                    const u32x2 d = *(gu32x2_t*)pu;
+                    d0[j] = d.x;
+                    d1[j] = d.y;
+                    d2[j] = 0u;
+                } else {                   // one 12-byte unit: rows 4q .. 4q + 11
+                    typedef unsigned u32x3 __attribute__((ext_vector_type(3), aligned(4)));
+                    typedef const __attribute__((address_space(1))) u32x3 gu32x3_t;
+                    const u32x3 d = *(gu32x3_t*)pu;
+                    d0[j] = d.x;
+                    d1[j] = d.y;
+                    d2[j] = d.z;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kOctPipe; ++j) {
+                const unsigned k = cv[j];   // bits 0..4: 8 (first row & 3)
+                const unsigned w0 = __builtin_amdgcn_alignbit(d1[j], d0[j], k);   // window rows 0..3
+                e0 += w0 & kM;
+                o0 += (w0 >> 8) & kM;
+                if constexpr (NR == 5) {
+                    r8 += __builtin_amdgcn_ubfe(d1[j], k, 8u);                    // row 4 (offset: k's bits 0..4)
+                } else {
+                    const unsigned w1 = __builtin_amdgcn_alignbit(d2[j], d1[j], k);   // rows 4..7
+                    e1 += w1 & kM;
+                    o1 += (w1 >> 8) & kM;
+                    r8 += __builtin_amdgcn_ubfe(d2[j], k, 8u);                    // row 8
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < NR - 1; ++r) {
+            const unsigned f = (r < 4) ? ((r & 1) ? o0 : e0) : ((r & 1) ? o1 : e1);
+            part[w][lane][r] = (int)((f >> (16 * ((r >> 1) & 1))) & 0xFFFFu);
+        }
+        part[w][lane][NR - 1] = (int)r8;
+    } else {
     const int per = (pl.Nv + kSupWaves - 1) / kSupWaves;
     const int lo = min(w * per, pl.Nv), cnt = min(per, pl.Nv - lo);
     const int* row = srow + lo;
@@ -1484,7 +1637,6 @@ __global__ __launch_bounds__(64 * kSupWaves) void k_super_oct(Items items, const
     constexpr u64 kM = 0x00FF00FF00FF00FFull;
     u64 ae = 0, ao = 0;
     unsigned a8 = 0;
-    constexpr int kOctPipe = oct_pipe<NR>();
     for (int i0 = 0; i0 < nq; i0 += kOctPipe) {
         u64 x[kOctPipe];
         unsigned y[kOctPipe];
@@ -1535,6 +1687,7 @@ __global__ __launch_bounds__(64 * kSupWaves) void k_super_oct(Items items, const
 #pragma unroll
     for (int r = 0; r < NR && r < 8; ++r) part[w][lane][r] = (int)(((r & 1) ? ao : ae) >> (16 * (r >> 1)) & 0xFFFFu);
     if constexpr (NR == 9) part[w][lane][8] = (int)a8;
+    }
     __syncthreads();
     if (w != 0) return;
     const int sbi = lane;
@@ -4564,6 +4717,38 @@ void enqueue_cost_patches(lgs_ctx* ctx, const BatchShape& B, Items d_items, cons
     LGS_HIP_CHECK(hipGetLastError());
 }
 
+// k_super_oct's packed gathers (PK): a row entry is the base << 3 and a
+// gather's byte offset 32 bits, so every unit index of every item (the
+// window's nsbx - 1 columns past a base included) must fit 27 bits -- a unit
+// buffer below 1.5 GiB.  Larger planes keep the unpacked loop.
+#ifndef LGS_OCT_PACKED
+#define LGS_OCT_PACKED 1
+#endif
+bool oct_packed_ok(const std::vector<MatchItem>& items)
+{
+    if (!LGS_OCT_PACKED) return false;
+    for (const auto& it : items)
+        if (!it.pl.oct || (long long)it.pl.low_res * it.pl.low_res * it.pl.pstrideO + 16 >= (1LL << 27)) return false;
+    return true;
+}
+
+// Certified fast rows (LGS_OPT_FAST_ROWS): the item's constants of the fast
+// chain, and whether fast_super_base's 24-bit multiplies hold its strides.
+void set_fast_rows(MatchItem& it, bool on)
+{
+    const RtcsmPlan& pl = it.pl;
+    const lgs_fast::ItemConsts k =
+        lgs_fast::item_consts(pl.sx, pl.sy, pl.min_x, pl.min_y, 1.0 / pl.res, it.geps, pl.win_x, pl.win_y);
+    it.fox = k.ox;
+    it.foy = k.oy;
+    it.fh0 = k.h0;
+    it.finv_lr = 1.0f / (float)pl.low_res;
+    it.fast = (on && pl.oct && pl.pstrideO < (1LL << 22) && pl.low_res >= 1 && pl.low_res < (1 << 20) &&
+               std::abs(pl.M) < (1 << 20) && k.h0 == k.h0)
+                  ? 1
+                  : 0;
+}
+
 // Enqueue the whole device pipeline of a batch of matches on ctx->stream: one
 // launch per stage for all items (d_items: the uploaded descriptors).
 // Options (reruns) apply to single-item batches only.
@@ -4676,13 +4861,22 @@ void enqueue_items(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::
     if (B.pruned) {
         {
             const int tok = ctx->timing_begin(K_SUPER, 8.0 * B.nsb2 * beams_T);
-            const size_t lds = sizeof(int) * ((size_t)std::max(B.NvMax, 1) + kOctRowPad);
+            // the packed loop's interleaved deal reads up to kSupWaves x nb x
+            // (its pipeline depth) entries past the row
+            const int oct_row_pad =
+                std::max(kOctRowPad, kSupWaves * (64 / std::max(items[0].pl.nsbx, 1)) * std::max(LGS_OCT_PIPE5, LGS_OCT_PIPE9));
+            const size_t lds = sizeof(int) * ((size_t)std::max(B.NvMax, 1) + (size_t)(B.oct ? oct_row_pad : kOctRowPad));
             dim3 g(B.chunks, B.Tmax, n);
+            const bool packed = B.oct && oct_packed_ok(items);
             if (ctx->skipped(K_SUPER)) {
-            } else if (B.oct && B.nsby <= 5)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_super_oct<5, 2>), g, dim3(64 * kSupWaves), lds, st, d_items, zero, ctx->dts(tok));
-            else if (B.oct)   // nsby 6..9: 12-row units (set_plane_layout)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_super_oct<9, 3>), g, dim3(64 * kSupWaves), lds, st, d_items, zero, ctx->dts(tok));
+            } else if (B.oct && B.nsby <= 5 && packed)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_super_oct<5, 2, 1>), g, dim3(64 * kSupWaves), lds, st, d_items, zero, ctx->dts(tok));
+            else if (B.oct && packed)   // nsby 6..9: 12-row units (set_plane_layout)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_super_oct<9, 3, 1>), g, dim3(64 * kSupWaves), lds, st, d_items, zero, ctx->dts(tok));
+            else if (B.oct && B.nsby <= 5)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_super_oct<5, 2, 0>), g, dim3(64 * kSupWaves), lds, st, d_items, zero, ctx->dts(tok));
+            else if (B.oct)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_super_oct<9, 3, 0>), g, dim3(64 * kSupWaves), lds, st, d_items, zero, ctx->dts(tok));
             else if (B.pair)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_super<1>), g, dim3(64 * kSupWaves), lds, st, d_items, zero);
             else
@@ -5192,6 +5386,7 @@ void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost
         it.inject = ctx->inject_index ? 1 : 0;
         it.geps = ctx->guard_eps;
         it.gcap = ctx->guard_cap;
+        set_fast_rows(it, ctx->fast_rows);
     }
     const bool lean = lean_rows(ctx, B, items);
     for (auto& it : items) it.lean = lean ? 1 : 0;

@@ -541,6 +541,7 @@ extern "C" int lgs_ctx_set_option(lgs_ctx* ctx, int option, double value)
     case LGS_OPT_DEVICE_HITS: ctx->device_hits = value != 0.0; return LGS_OK;
     case LGS_OPT_ZERO_TILES: ctx->zero_tiles = value != 0.0; return LGS_OK;
     case LGS_OPT_LEAN_PROJECT: ctx->lean_project = value != 0.0; return LGS_OK;
+    case LGS_OPT_FAST_ROWS: ctx->fast_rows = value != 0.0; return LGS_OK;
     case LGS_OPT_PGCG_GRID_NODES:
         if (!(value >= 0.0)) return LGS_ERR_INVALID_ARG;
         ctx->pg_grid_nodes = (int)std::min(value, 2147483647.0);

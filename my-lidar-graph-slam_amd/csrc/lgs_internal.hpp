@@ -344,6 +344,7 @@ struct lgs_ctx {
     bool fused_planes = true;    // superblock units by k_super_hv (LGS_OPT_FUSED_PLANES)
     int seed_wide = 12;
     bool lean_project = true;    // LGS_OPT_LEAN_PROJECT (k_rtcsm.hip lean_rows)
+    bool fast_rows = true;       // LGS_OPT_FAST_ROWS (k_rtcsm.hip lean_super_row)
     bool zero_tiles = true;   // LGS_OPT_ZERO_TILES          // batches: candidate superblocks whose best members seed the bound (LGS_OPT_SEED_WIDE; <= 4: one launch)
     bool device_hits = true;     // map rebuilds of many scans: hit points / ray cells on the device (LGS_OPT_DEVICE_HITS)
     bool split_chunks = false;   // calls of 32..64 matches as two chunks (LGS_OPT_SPLIT_CHUNKS; measured r05, 8-rank loop block: 1.007 vs 0.869 ms as one)
