@@ -20,6 +20,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_gs
 	$(MAKE) -C tests/cpp_hc
 	$(MAKE) -C tests/cpp_hc_sq
+	$(MAKE) -C tests/cpp_loop_sq
 	$(MAKE) -C tests/cpp_pgcg
 	$(MAKE) -C tests/cpp_pglm
 
@@ -32,6 +33,7 @@ clean:
 	$(MAKE) -C tests/cpp_gs clean
 	$(MAKE) -C tests/cpp_hc clean
 	$(MAKE) -C tests/cpp_hc_sq clean
+	$(MAKE) -C tests/cpp_loop_sq clean
 	$(MAKE) -C tests/cpp_pgcg clean
 	$(MAKE) -C tests/cpp_pglm clean
 

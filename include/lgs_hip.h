@@ -823,6 +823,81 @@ int  lgs_hc_sq_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* const* grids, c
 int  lgs_hc_sq_trace(lgs_ctx* ctx, const lgs_grid* grid, const lgs_hc_params* params, const lgs_cost_sq_params* cost,
                      const lgs_scan* scan, lgs_pose2d initial_pose, int* moves, double* costs, int cap);
 
+/* ---- search matchers and loop detectors with either cost function ----
+ * The `_cost` entry points take an lgs_cost_spec where their namesakes take
+ * an lgs_cost_ge_params; every other argument is the namesake's.
+ *   kind == LGS_COST_GREEDY_ENDPOINT  the namesake's path and the namesake's
+ *     bytes (spec->ge is what it would have been given).
+ *   kind == LGS_COST_SQUARE_ERROR     normalized_cost = CostSquareError::Cost(
+ *     best_sensor_pose) / NumOfScans() and covariance = ComputeCovariance(
+ *     best_sensor_pose) with spec->sq, whether or not a pose was found (as
+ *     lgs_summaries_apply_cost_sq gives, bit for bit); every other summary
+ *     field is the namesake's, except the diagnostic counters guard_hits and
+ *     fixups, which no longer count the greedy-endpoint stage's cells.  A loop
+ *     record differs from the namesake's in normalized_cost and covariance
+ *     only.  The correlative matcher evaluates the cost as a stage of its own
+ *     pipeline, at the best pose the search left on the device (k_cost_sq: no
+ *     greedy-endpoint stage, no second synchronisation); the branch-and-bound
+ *     and grid-search matchers run one k_sq_cost_batch launch per call.
+ * An unknown kind or non-finite usable ranges: LGS_ERR_INVALID_ARG before any
+ * device work.  The caps and status codes of lgs_cost_square_error_batch
+ * apply (a map of 2^30 cells or more: LGS_ERR_INVALID_ARG; an angle outside
+ * the restated sincos domain: LGS_ERR_INTERNAL); with kind 1 a failing call
+ * writes nothing to `out` / `results`. */
+#define LGS_COST_GREEDY_ENDPOINT 0
+#define LGS_COST_SQUARE_ERROR    1
+typedef struct {
+    int kind;                 /* LGS_COST_* */
+    lgs_cost_ge_params ge;    /* read when kind == 0 */
+    lgs_cost_sq_params sq;    /* read when kind == 1 */
+} lgs_cost_spec;
+size_t lgs_cost_spec_size(void);   /* sizeof(lgs_cost_spec), for bindings */
+
+int  lgs_rtcsm_optimize_pose_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* coarse,
+                                  const lgs_rtcsm_params* params, const lgs_cost_spec* cost,
+                                  const lgs_scan* scan, lgs_pose2d initial_pose,
+                                  double normalized_score_threshold, lgs_rtcsm_summary* out);
+int  lgs_rtcsm_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_rtcsm_params* params,
+                                        const lgs_cost_spec* cost, const lgs_scan* scan,
+                                        lgs_pose2d initial_pose, lgs_rtcsm_summary* out);
+int  lgs_rtcsm_optimize_pose_query_batch_cost(lgs_ctx* ctx, const lgs_grid* const* grids,
+                                              const lgs_rtcsm_params* params, const lgs_cost_spec* cost,
+                                              const lgs_scan* const* scans, const lgs_pose2d* initial_poses,
+                                              int n, lgs_rtcsm_summary* out);
+int  lgs_rtcsm_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* coarse,
+                                        const lgs_rtcsm_params* params, const lgs_cost_spec* cost,
+                                        const lgs_scan* const* scans, const lgs_pose2d* initial_poses,
+                                        int n, double normalized_score_threshold, lgs_rtcsm_summary* out);
+int  lgs_bb_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* const* pyramid,
+                                     const lgs_bb_params* params, const lgs_cost_spec* cost,
+                                     const lgs_scan* const* scans, const lgs_pose2d* initial_poses, int n,
+                                     double normalized_score_threshold, lgs_rtcsm_summary* out);
+int  lgs_bb_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_bb_params* params,
+                                     const lgs_cost_spec* cost, const lgs_scan* scan,
+                                     lgs_pose2d initial_pose, lgs_rtcsm_summary* out);
+int  lgs_gs_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
+                                     const lgs_cost_spec* cost, const lgs_scan* const* scans,
+                                     const lgs_pose2d* initial_poses, int n, double normalized_score_threshold,
+                                     lgs_rtcsm_summary* out);
+int  lgs_gs_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
+                                     const lgs_cost_spec* cost, const lgs_scan* scan, lgs_pose2d initial_pose,
+                                     lgs_rtcsm_summary* out);
+int  lgs_loop_detect_rtcsm_cost(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_spec* cost,
+                                double score_threshold, const lgs_loop_query* queries, int num_queries,
+                                const lgs_loop_candidate* candidates, int num_candidates,
+                                lgs_loop_result* results);
+int  lgs_loop_detect_rtcsm_multi_cost(lgs_ctx* const* ctxs, int num_ctx, const lgs_rtcsm_params* params,
+                                      const lgs_cost_spec* cost, double score_threshold,
+                                      const lgs_loop_query* queries, int num_queries,
+                                      const lgs_loop_candidate* candidates, int num_candidates,
+                                      lgs_loop_result* results);
+int  lgs_loop_detect_bb_cost(lgs_ctx* ctx, const lgs_bb_params* params, const lgs_cost_spec* cost,
+                             double score_threshold, const lgs_loop_query* queries, int num_queries,
+                             const lgs_loop_candidate* candidates, int num_candidates, lgs_loop_result* results);
+int  lgs_loop_detect_gs_cost(lgs_ctx* ctx, const lgs_gs_params* params, const lgs_cost_spec* cost,
+                             double score_threshold, const lgs_loop_query* queries, int num_queries,
+                             const lgs_loop_candidate* candidates, int num_candidates, lgs_loop_result* results);
+
 /* ---- the pose graph's conjugate-gradient step (k_pgcg.hip) ----
  * H x = rhs for the symmetric matrix of a pose-graph Levenberg-Marquardt step
  * (PoseGraphOptimizerLM::OptimizeStep, C/mapping/pose_graph_optimizer_lm.cpp:

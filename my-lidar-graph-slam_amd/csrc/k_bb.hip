@@ -483,7 +483,7 @@ struct BBLevel {
 // first descent changed the threshold the superset was built with).
 void run_bb(lgs_ctx* ctx, const lgs_bb_params* p, const lgs_cost_ge_params* cost, const lgs_grid* const* grids,
             const double* const* const* pyr, lgs_scan* const* scans, const lgs_pose2d* init, int n, double nthr,
-            lgs_rtcsm_summary* out, bool no_path = false)
+            lgs_rtcsm_summary* out, bool no_path = false, const lgs_cost_sq_params* sq = nullptr)
 {
     for (int k = 0; k < n; ++k) grid_acquire(ctx, grids[k]);
     LGS_HIP_CHECK(hipSetDevice(ctx->device));
@@ -878,6 +878,22 @@ void run_bb(lgs_ctx* ctx, const lgs_bb_params* p, const lgs_cost_ge_params* cost
     // cost and covariance at the best poses (:146-153), grouped by map
     std::vector<int> order, redo;
     for (int j = 0; j < n; ++j) (failed[(size_t)j] ? redo : order).push_back(j);
+    if (sq) {
+        // CostSquareError: one launch over every item, whatever its map
+        std::vector<const lgs_grid*> gs;
+        std::vector<lgs_scan*> sc;
+        std::vector<lgs_pose2d> bp;
+        std::vector<lgs_rtcsm_summary> tmp;
+        for (int j : order) {
+            gs.push_back(grids[j]);
+            sc.push_back(scans[j]);
+            bp.push_back(best[j]);
+            tmp.push_back(out[j]);
+        }
+        cost_summaries_sq(ctx, gs.data(), sq, sc.data(), bp.data(), (int)order.size(), tmp.data());
+        for (size_t k = 0; k < order.size(); ++k) out[order[k]] = tmp[k];
+        order.clear();
+    }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return grids[a] < grids[b]; });
     for (size_t k0 = 0; k0 < order.size();) {
         size_t k1 = k0;
@@ -913,7 +929,7 @@ void run_bb(lgs_ctx* ctx, const lgs_bb_params* p, const lgs_cost_ge_params* cost
             i2.push_back(init[j]);
         }
         std::vector<lgs_rtcsm_summary> o2(redo.size());
-        run_bb(ctx, p, cost, g2.data(), p2.data(), s2.data(), i2.data(), (int)redo.size(), nthr, o2.data(), true);
+        run_bb(ctx, p, cost, g2.data(), p2.data(), s2.data(), i2.data(), (int)redo.size(), nthr, o2.data(), true, sq);
         for (size_t k = 0; k < redo.size(); ++k) out[redo[k]] = o2[k];
     }
 }
@@ -963,15 +979,17 @@ extern "C" int lgs_grid_precompute_pyramid(lgs_ctx* ctx, const lgs_grid* in, int
     });
 }
 
-extern "C" int lgs_bb_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* const* pyramid,
-                                          const lgs_bb_params* params, const lgs_cost_ge_params* cost,
-                                          const lgs_scan* const* scans, const lgs_pose2d* initial, int n,
-                                          double nthr, lgs_rtcsm_summary* out)
+// sq non-null: the cost step is CostSquareError's (k_sq_cost_batch)
+static int bb_batch_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* const* pyramid,
+                        const lgs_bb_params* params, const lgs_cost_ge_params* cost, const lgs_cost_sq_params* sq,
+                        const lgs_scan* const* scans, const lgs_pose2d* initial, int n, double nthr,
+                        lgs_rtcsm_summary* out)
 {
     if (!ctx || !grid || !pyramid || !scans || !initial || !out || n < 0) return LGS_ERR_INVALID_ARG;
     if (n == 0) return LGS_OK;
     return guarded(ctx, [&] {
         check_bb(params, cost);
+        LGS_REQUIRE(!sq || (long long)grid->w * grid->h < (1LL << 30), "square-error cost: map of 2^30 cells or more");
         std::vector<const double*> pyr;
         for (int h = 0; h <= params->node_height_max; ++h) {
             LGS_REQUIRE(pyramid[h] && pyramid[h]->w == grid->w && pyramid[h]->h == grid->h,
@@ -988,8 +1006,50 @@ extern "C" int lgs_bb_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, co
         for (int j0 = 0; j0 < n; j0 += kBBBatch) {
             const int m = std::min(kBBBatch, n - j0);
             run_bb(ctx, params, cost, grids.data() + j0, pp.data() + j0, sc.data() + j0, initial + j0, m, nthr,
-                   out + j0);
+                   out + j0, false, sq);
         }
+    });
+}
+
+extern "C" int lgs_bb_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* const* pyramid,
+                                          const lgs_bb_params* params, const lgs_cost_ge_params* cost,
+                                          const lgs_scan* const* scans, const lgs_pose2d* initial, int n,
+                                          double nthr, lgs_rtcsm_summary* out)
+{
+    return bb_batch_run(ctx, grid, pyramid, params, cost, nullptr, scans, initial, n, nthr, out);
+}
+
+// With the square-error cost a failing call leaves `out` as it found it.
+extern "C" int lgs_bb_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* const* pyramid,
+                                               const lgs_bb_params* params, const lgs_cost_spec* cost,
+                                               const lgs_scan* const* scans, const lgs_pose2d* initial, int n,
+                                               double nthr, lgs_rtcsm_summary* out)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq) return lgs_bb_optimize_pose_batch(ctx, grid, pyramid, params, sel.ge, scans, initial, n, nthr, out);
+    if (!out || n < 0) return LGS_ERR_INVALID_ARG;
+    std::vector<lgs_rtcsm_summary> tmp;
+    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)n); });
+    if (rc0 != LGS_OK) return rc0;
+    const int rc = bb_batch_run(ctx, grid, pyramid, params, sel.ge, sel.sq, scans, initial, n, nthr, tmp.data());
+    if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(lgs_rtcsm_summary) * (size_t)n);
+    return rc;
+}
+
+static int bb_query_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_bb_params* params,
+                        const lgs_cost_ge_params* cost, const lgs_cost_sq_params* sq, const lgs_scan* scan,
+                        lgs_pose2d initial, lgs_rtcsm_summary* out)
+{
+    if (!ctx || !grid || !scan || !out) return LGS_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        check_bb(params, cost);
+        LGS_REQUIRE(scan->n >= 1, "empty scan");
+        LGS_REQUIRE(!sq || (long long)grid->w * grid->h < (1LL << 30), "square-error cost: map of 2^30 cells or more");
+        auto pyr = pyramids(ctx, &grid, 1, params->node_height_max);   // ComputeCoarserMaps (:157-165)
+        const double* const* pp = pyr[0].data();
+        lgs_scan* s = const_cast<lgs_scan*>(scan);
+        run_bb(ctx, params, cost, &grid, &pp, &s, &initial, 1, DBL_MIN, out, false, sq);
     });
 }
 
@@ -997,21 +1057,27 @@ extern "C" int lgs_bb_optimize_pose_query(lgs_ctx* ctx, const lgs_grid* grid, co
                                           const lgs_cost_ge_params* cost, const lgs_scan* scan,
                                           lgs_pose2d initial, lgs_rtcsm_summary* out)
 {
-    if (!ctx || !grid || !scan || !out) return LGS_ERR_INVALID_ARG;
-    return guarded(ctx, [&] {
-        check_bb(params, cost);
-        LGS_REQUIRE(scan->n >= 1, "empty scan");
-        auto pyr = pyramids(ctx, &grid, 1, params->node_height_max);   // ComputeCoarserMaps (:157-165)
-        const double* const* pp = pyr[0].data();
-        lgs_scan* s = const_cast<lgs_scan*>(scan);
-        run_bb(ctx, params, cost, &grid, &pp, &s, &initial, 1, DBL_MIN, out);
-    });
+    return bb_query_run(ctx, grid, params, cost, nullptr, scan, initial, out);
 }
 
-extern "C" int lgs_loop_detect_bb(lgs_ctx* ctx, const lgs_bb_params* params, const lgs_cost_ge_params* cost,
-                                  double score_threshold, const lgs_loop_query* queries, int num_queries,
-                                  const lgs_loop_candidate* candidates, int num_candidates,
-                                  lgs_loop_result* results)
+extern "C" int lgs_bb_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_bb_params* params,
+                                               const lgs_cost_spec* cost, const lgs_scan* scan, lgs_pose2d initial,
+                                               lgs_rtcsm_summary* out)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq) return lgs_bb_optimize_pose_query(ctx, grid, params, sel.ge, scan, initial, out);
+    if (!out) return LGS_ERR_INVALID_ARG;
+    lgs_rtcsm_summary tmp;
+    const int rc = bb_query_run(ctx, grid, params, sel.ge, sel.sq, scan, initial, &tmp);
+    if (rc == LGS_OK) *out = tmp;
+    return rc;
+}
+
+static int loop_detect_bb_run(lgs_ctx* ctx, const lgs_bb_params* params, const lgs_cost_ge_params* cost,
+                              const lgs_cost_sq_params* sq, double score_threshold, const lgs_loop_query* queries,
+                              int num_queries, const lgs_loop_candidate* candidates, int num_candidates,
+                              lgs_loop_result* results)
 {
     if (!ctx || !params || !cost || (num_queries > 0 && !queries) || num_queries < 0 || num_candidates < 0 ||
         (num_candidates > 0 && (!candidates || !results)))
@@ -1023,6 +1089,8 @@ extern "C" int lgs_loop_detect_bb(lgs_ctx* ctx, const lgs_bb_params* params, con
         for (int q = 0; q < num_queries; ++q) {
             const lgs_loop_query& Q = queries[q];
             LGS_REQUIRE(Q.map, "loop query without a local map");
+            LGS_REQUIRE(!sq || (long long)Q.map->w * Q.map->h < (1LL << 30),
+                        "square-error cost: map of 2^30 cells or more");
             LGS_REQUIRE(Q.first_candidate == covered && Q.num_candidates >= 0 &&
                             Q.first_candidate + Q.num_candidates <= num_candidates,
                         "loop queries must cover the candidates contiguously and in order");
@@ -1058,7 +1126,7 @@ extern "C" int lgs_loop_detect_bb(lgs_ctx* ctx, const lgs_bb_params* params, con
             std::vector<lgs_rtcsm_summary> sums(cand.size());
             if (!cand.empty())
                 run_bb(ctx, params, cost, grids.data(), pp.data(), sc.data(), poses.data(), (int)cand.size(),
-                       score_threshold, sums.data());
+                       score_threshold, sums.data(), false, sq);
             for (size_t k = 0; k < cand.size(); ++k) {
                 const lgs_loop_query& Q = queries[qof[k]];
                 lgs_loop_result& r = results[cand[k]];
@@ -1077,4 +1145,34 @@ extern "C" int lgs_loop_detect_bb(lgs_ctx* ctx, const lgs_bb_params* params, con
             q0 = q1;
         }
     });
+}
+
+extern "C" int lgs_loop_detect_bb(lgs_ctx* ctx, const lgs_bb_params* params, const lgs_cost_ge_params* cost,
+                                  double score_threshold, const lgs_loop_query* queries, int num_queries,
+                                  const lgs_loop_candidate* candidates, int num_candidates,
+                                  lgs_loop_result* results)
+{
+    return loop_detect_bb_run(ctx, params, cost, nullptr, score_threshold, queries, num_queries, candidates,
+                              num_candidates, results);
+}
+
+// With the square-error cost a failing call leaves `results` as it found them.
+extern "C" int lgs_loop_detect_bb_cost(lgs_ctx* ctx, const lgs_bb_params* params, const lgs_cost_spec* cost,
+                                       double score_threshold, const lgs_loop_query* queries, int num_queries,
+                                       const lgs_loop_candidate* candidates, int num_candidates,
+                                       lgs_loop_result* results)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq)
+        return lgs_loop_detect_bb(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
+                                  num_candidates, results);
+    if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
+    std::vector<lgs_loop_result> tmp;
+    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
+    if (rc0 != LGS_OK) return rc0;
+    const int rc = loop_detect_bb_run(ctx, params, sel.ge, sel.sq, score_threshold, queries, num_queries, candidates,
+                                      num_candidates, tmp.data());
+    if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
+    return rc;
 }

@@ -333,7 +333,7 @@ size_t gs_item_bytes(const GSWindow& w, int Nvp)
 // every pose's score in (iy, ix, it) order; no summaries then (cost == null).
 void run_gs(lgs_ctx* ctx, const lgs_gs_params* p, const lgs_cost_ge_params* cost, const GSWindow& win,
             const lgs_grid* const* grids, lgs_scan* const* scans, const lgs_pose2d* init, int n, double nthr,
-            lgs_rtcsm_summary* out, double* dense_host = nullptr)
+            lgs_rtcsm_summary* out, double* dense_host = nullptr, const lgs_cost_sq_params* sq = nullptr)
 {
     const int nx = (int)win.dx.size(), ny = (int)win.dy.size(), nt = (int)win.dt.size();
     const long long poses = win.poses();
@@ -501,6 +501,11 @@ void run_gs(lgs_ctx* ctx, const lgs_gs_params* p, const lgs_cost_ge_params* cost
         o.fine_blocks = 0;
         best[(size_t)j] = bp;
     }
+    if (sq) {
+        // CostSquareError (:99-110): one launch over every item, whatever its map
+        cost_summaries_sq(ctx, grids, sq, scans, best.data(), n, out);
+        return;
+    }
     // cost and covariance at the best poses (:99-110), grouped by map
     std::vector<int> order((size_t)n);
     for (int j = 0; j < n; ++j) order[(size_t)j] = j;
@@ -537,9 +542,10 @@ extern "C" int lgs_gs_steps(double range, double step, double* out, int cap)
     }
 }
 
-extern "C" int lgs_gs_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
-                                          const lgs_cost_ge_params* cost, const lgs_scan* const* scans,
-                                          const lgs_pose2d* initial, int n, double nthr, lgs_rtcsm_summary* out)
+// sq non-null: the cost step is CostSquareError's (k_sq_cost_batch)
+static int gs_batch_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
+                        const lgs_cost_ge_params* cost, const lgs_cost_sq_params* sq, const lgs_scan* const* scans,
+                        const lgs_pose2d* initial, int n, double nthr, lgs_rtcsm_summary* out)
 {
     if (!ctx || !grid || !params || !cost || n < 0 || (n > 0 && (!scans || !initial || !out)))
         return LGS_ERR_INVALID_ARG;
@@ -553,8 +559,40 @@ extern "C" int lgs_gs_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, co
             LGS_REQUIRE(scans[j] && scans[j]->n >= 1, "empty scan");
             sc[(size_t)j] = const_cast<lgs_scan*>(scans[j]);
         }
-        run_gs(ctx, params, cost, win, grids.data(), sc.data(), initial, n, nthr, out);
+        run_gs(ctx, params, cost, win, grids.data(), sc.data(), initial, n, nthr, out, nullptr, sq);
     });
+}
+
+extern "C" int lgs_gs_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
+                                          const lgs_cost_ge_params* cost, const lgs_scan* const* scans,
+                                          const lgs_pose2d* initial, int n, double nthr, lgs_rtcsm_summary* out)
+{
+    return gs_batch_run(ctx, grid, params, cost, nullptr, scans, initial, n, nthr, out);
+}
+
+// With the square-error cost a failing call leaves `out` as it found it.
+extern "C" int lgs_gs_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
+                                               const lgs_cost_spec* cost, const lgs_scan* const* scans,
+                                               const lgs_pose2d* initial, int n, double nthr, lgs_rtcsm_summary* out)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq) return lgs_gs_optimize_pose_batch(ctx, grid, params, sel.ge, scans, initial, n, nthr, out);
+    if (n < 0 || (n > 0 && !out)) return LGS_ERR_INVALID_ARG;
+    std::vector<lgs_rtcsm_summary> tmp;
+    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)n); });
+    if (rc0 != LGS_OK) return rc0;
+    const int rc = gs_batch_run(ctx, grid, params, sel.ge, sel.sq, scans, initial, n, nthr, tmp.data());
+    if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(lgs_rtcsm_summary) * (size_t)n);
+    return rc;
+}
+
+extern "C" int lgs_gs_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
+                                               const lgs_cost_spec* cost, const lgs_scan* scan, lgs_pose2d initial,
+                                               lgs_rtcsm_summary* out)
+{
+    if (!scan) return LGS_ERR_INVALID_ARG;
+    return lgs_gs_optimize_pose_batch_cost(ctx, grid, params, cost, &scan, &initial, 1, DBL_MIN, out);
 }
 
 extern "C" int lgs_gs_optimize_pose_query(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
@@ -580,10 +618,10 @@ extern "C" int lgs_gs_dense_scores(lgs_ctx* ctx, const lgs_grid* grid, const lgs
     });
 }
 
-extern "C" int lgs_loop_detect_gs(lgs_ctx* ctx, const lgs_gs_params* params, const lgs_cost_ge_params* cost,
-                                  double score_threshold, const lgs_loop_query* queries, int num_queries,
-                                  const lgs_loop_candidate* candidates, int num_candidates,
-                                  lgs_loop_result* results)
+static int loop_detect_gs_run(lgs_ctx* ctx, const lgs_gs_params* params, const lgs_cost_ge_params* cost,
+                              const lgs_cost_sq_params* sq, double score_threshold, const lgs_loop_query* queries,
+                              int num_queries, const lgs_loop_candidate* candidates, int num_candidates,
+                              lgs_loop_result* results)
 {
     if (!ctx || !params || !cost || (num_queries > 0 && !queries) || num_queries < 0 || num_candidates < 0 ||
         (num_candidates > 0 && (!candidates || !results)))
@@ -617,7 +655,7 @@ extern "C" int lgs_loop_detect_gs(lgs_ctx* ctx, const lgs_gs_params* params, con
         if (num_candidates == 0) return;
         std::vector<lgs_rtcsm_summary> sums((size_t)num_candidates);
         run_gs(ctx, params, cost, win, grids.data(), sc.data(), poses.data(), num_candidates, score_threshold,
-               sums.data());
+               sums.data(), nullptr, sq);
         for (int k = 0; k < num_candidates; ++k) {
             const lgs_loop_query& Q = queries[qof[(size_t)k]];
             const lgs_rtcsm_summary& s = sums[(size_t)k];
@@ -634,4 +672,34 @@ extern "C" int lgs_loop_detect_gs(lgs_ctx* ctx, const lgs_gs_params* params, con
             std::memcpy(r.covariance, s.covariance, sizeof(r.covariance));
         }
     });
+}
+
+extern "C" int lgs_loop_detect_gs(lgs_ctx* ctx, const lgs_gs_params* params, const lgs_cost_ge_params* cost,
+                                  double score_threshold, const lgs_loop_query* queries, int num_queries,
+                                  const lgs_loop_candidate* candidates, int num_candidates,
+                                  lgs_loop_result* results)
+{
+    return loop_detect_gs_run(ctx, params, cost, nullptr, score_threshold, queries, num_queries, candidates,
+                              num_candidates, results);
+}
+
+// With the square-error cost a failing call leaves `results` as it found them.
+extern "C" int lgs_loop_detect_gs_cost(lgs_ctx* ctx, const lgs_gs_params* params, const lgs_cost_spec* cost,
+                                       double score_threshold, const lgs_loop_query* queries, int num_queries,
+                                       const lgs_loop_candidate* candidates, int num_candidates,
+                                       lgs_loop_result* results)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq)
+        return lgs_loop_detect_gs(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
+                                  num_candidates, results);
+    if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
+    std::vector<lgs_loop_result> tmp;
+    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
+    if (rc0 != LGS_OK) return rc0;
+    const int rc = loop_detect_gs_run(ctx, params, sel.ge, sel.sq, score_threshold, queries, num_queries, candidates,
+                                      num_candidates, tmp.data());
+    if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
+    return rc;
 }

@@ -29,7 +29,7 @@
 // summary's pose algebra are formed on the host with glibc.
 #include "lgs_internal.hpp"
 #include "glibc_math.hpp"
-#include "sq_cost_device.hpp"
+#include "sq_cost_stage.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -39,11 +39,8 @@ using namespace lgs;
 
 namespace {
 
-constexpr int kSqThreads = 768;   // 12 waves: with 165 VGPRs a CU holds 3 waves per SIMD, one such workgroup
 constexpr int kSqPoses = 6;                  // poses per cost pass (the six neighbours)
-constexpr int kSqGradRows = 4;               // cost term and the three gradient terms of a beam
 constexpr int kSqMaxIter = 65536;            // documented cap of max_iterations
-constexpr size_t kSqLdsMax = 144 * 1024;     // term rows in LDS up to here, else global rows
 constexpr size_t kSqRowsCap = size_t(1) << 30;   // global term rows of the matches of one launch
 constexpr int kSqChunk = 4096;               // items per launch
 
@@ -55,18 +52,6 @@ struct SqRecord {
     int num_iterations, num_refinements, passes, cost_evals;
 };
 
-// One item of a launch (device memory).
-struct SqItem {
-    LsPlan p;                   // map geometry; cost_min / cost_max hold the beam filter (:27-30)
-    double sx, sy, st;          // sensor pose
-    const double* map;
-    const double* ranges;
-    const double* angles;
-    double* rows;               // term rows when they do not fit LDS
-    int* trace_move;            // [pass cap] or null
-    double* trace_cost;
-};
-
 // What every item of a launch shares.
 struct SqShared {
     double lin_step, ang_step;
@@ -74,54 +59,6 @@ struct SqShared {
     int nrows;                  // term rows per item: 6 (walk), 4 (cost and gradient), 1 (cost)
     unsigned lds_bytes;         // dynamic LDS of the launch
 };
-
-// pow(1.0 - S, 2.0) of beam i at `pose` (:32-55), +0.0 for a filtered beam
-__device__ __forceinline__ double sq_term(const SqItem& it, int i, const double pose[3], int* __restrict__ err)
-{
-    const double r = gload(it.ranges + i);
-    if (r >= it.p.cost_max || r <= it.p.cost_min) return 0.0;   // :35-36
-    const double a = gload(it.angles + i);
-    if (!glm::gl_sincos_ok(pose[2] + a)) *err = 1;
-    double sn, cs, fx, fy;
-    beam_cell(it.p, pose, r, a, sn, cs, fx, fy);
-    const Axis ax = make_axis(fx, it.p.W), ay = make_axis(fy, it.p.H);
-    const double e = 1.0 - smoothed(it.map, it.p.W, ax, ay);
-    return e * e;   // GCC folds pow(x, 2.0) to the exact product
-}
-
-// the cost term and the three terms 2.0 * e * (-g_k) of ComputeGradient (:84-104)
-__device__ __forceinline__ void sq_grad_terms(const SqItem& it, int i, const double pose[3], double (&t)[kSqGradRows],
-                                              int* __restrict__ err)
-{
-#pragma unroll
-    for (int k = 0; k < kSqGradRows; ++k) t[k] = 0.0;
-    const double r = gload(it.ranges + i);
-    if (r >= it.p.cost_max || r <= it.p.cost_min) return;
-    const double a = gload(it.angles + i);
-    if (!glm::gl_sincos_ok(pose[2] + a)) *err = 1;
-    double e, gv[3];
-    beam_terms(it.p, it.map, pose, r, a, e, gv);
-    t[0] = e * e;
-    t[1] = 2.0 * e * (-gv[0]);
-    t[2] = 2.0 * e * (-gv[1]);
-    t[3] = 2.0 * e * (-gv[2]);
-}
-
-// c = 0.0; c += term, beams in order (:23, :55; :70-72, :100-104)
-__device__ __forceinline__ double sq_chain(const double* __restrict__ row, int N)
-{
-    double c = 0.0;
-    int i = 0;
-    for (; i + 8 <= N; i += 8) {
-        double t[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = row[i + j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) c += t[j];
-    }
-    for (; i < N; ++i) c += row[i];
-    return c;
-}
 
 // Diagnostics build (make probe): thread 0 of block 0 adds up the 100 MHz wall
 // clock of the two phases of sq_costs and prints the sums after the walk.
@@ -162,33 +99,6 @@ __device__ __forceinline__ void sq_costs(const SqItem& it, double (*s_pose)[3], 
     SQ_PROBE_T(2);
     SQ_PROBE_ADD(0, 0, 1);
     SQ_PROBE_ADD(1, 1, 2);
-}
-
-// Cost and ComputeGradient's three sums at s_pose[0] into s_cost[0..3]: lanes
-// 0..3 of wave 0 add the four rows in beam order.  Ends with a barrier.
-__device__ __forceinline__ void sq_cost_grad(const SqItem& it, double (*s_pose)[3], double* s_cost, double* l_rows,
-                                             bool in_lds, int* __restrict__ err)
-{
-    const int N = it.p.N;
-    double* __restrict__ g_rows = it.rows;
-    const double pose[3] = { s_pose[0][0], s_pose[0][1], s_pose[0][2] };
-    for (int i = threadIdx.x; i < N; i += kSqThreads) {
-        double t[kSqGradRows];
-        sq_grad_terms(it, i, pose, t, err);
-#pragma unroll
-        for (int k = 0; k < kSqGradRows; ++k) {
-            if (in_lds)
-                l_rows[(size_t)k * N + i] = t[k];
-            else
-                g_rows[(size_t)k * N + i] = t[k];
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < kSqGradRows) {
-        const size_t o = (size_t)threadIdx.x * N;
-        s_cost[threadIdx.x] = in_lds ? sq_chain(l_rows + o, N) : sq_chain(g_rows + o, N);
-    }
-    __syncthreads();
 }
 
 // the six neighbour poses of a pass (:62-69): all three additions performed
@@ -363,17 +273,6 @@ void check_hc(const lgs_hc_params* p)
     LGS_REQUIRE(p->max_iterations <= kSqMaxIter, "hill climbing: more than 65536 iterations");
 }
 
-template <class K>
-void sq_allow_lds(K kernel, size_t bytes)
-{
-    // dynamic LDS beyond the 64 KiB default has to be announced; launches
-    // report what this leaves unsaid
-    if (bytes > 64 * 1024) {
-        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        (void)hipGetLastError();
-    }
-}
-
 SqItem sq_item(const lgs_grid* g, const lgs_cost_sq_params* cost, const lgs_scan* s, lgs_pose2d sensor)
 {
     SqItem it;
@@ -508,16 +407,6 @@ void run_sq(lgs_ctx* ctx, const lgs_hc_params* p, bool want_grad, const lgs_cost
     }
 }
 
-// ComputeCovariance (:112-135): g g^T, + 0.01 on the diagonal
-void sq_covariance(const double g[3], double* cov)
-{
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) cov[3 * a + b] = g[a] * g[b];
-    cov[0] += 0.01;
-    cov[4] += 0.01;
-    cov[8] += 0.01;
-}
-
 void run_hc_sq(lgs_ctx* ctx, const lgs_hc_params* p, const lgs_cost_sq_params* cost, const lgs_grid* const* grids,
                const lgs_scan* const* scans, const lgs_pose2d* init, int n, lgs_hc_summary* out,
                int* trace_moves = nullptr, double* trace_costs = nullptr, int trace_cap = 0)
@@ -552,6 +441,26 @@ void run_hc_sq(lgs_ctx* ctx, const lgs_hc_params* p, const lgs_cost_sq_params* c
 }
 
 }  // namespace
+
+namespace lgs {
+// What the branch-and-bound and grid-search matchers derive from their cost
+// function after the search (scan_matcher_branch_bound.cpp:146-153,
+// scan_matcher_grid_search.cpp:97-107) when that function is CostSquareError:
+// normalized cost, estimated pose and covariance at best[j], one
+// k_sq_cost_batch launch over all n items (their maps may differ).
+void cost_summaries_sq(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_sq_params* cost,
+                       lgs_scan* const* scans, const lgs_pose2d* best, int n, lgs_rtcsm_summary* out)
+{
+    if (n <= 0) return;
+    std::vector<SqRecord> recs((size_t)n);
+    run_sq(ctx, nullptr, true, cost, grids, scans, best, n, recs.data());
+    for (int j = 0; j < n; ++j) {
+        out[j].normalized_cost = recs[(size_t)j].min_cost / (double)scans[j]->n;
+        out[j].estimated_pose = move_backward(best[j], scans[j]->rel);
+        sq_covariance(recs[(size_t)j].grad, out[j].covariance);
+    }
+}
+}  // namespace lgs
 
 extern "C" int lgs_cost_square_error_batch(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_sq_params* cost,
                                            const lgs_scan* const* scans, const lgs_pose2d* sensor_poses, int n,

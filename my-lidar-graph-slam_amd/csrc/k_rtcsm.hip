@@ -27,8 +27,12 @@
 //               the host for an exact dense rerun.
 //   k_cost_*    CostGreedyEndpoint::Cost at the best pose and its six
 //               central-difference neighbours (C/mapping/cost_function_greedy_endpoint.cpp:32-171).
+//   k_cost_sq   in their place for a matcher built with CostSquareError: Cost
+//               and ComputeGradient's sums at the best pose
+//               (C/mapping/cost_function_square_error.cpp:21-109).
 #include "lgs_internal.hpp"
 #include "fast_cell.hpp"
+#include "sq_cost_stage.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -3681,6 +3685,66 @@ __global__ __launch_bounds__(kCostThreads) void k_cost(Items items, int guard_ca
 #define KCOST(ks) ((ks) == 1 ? k_cost<1> : k_cost<0>)
 
 // --------------------------------------------------------------------------
+// square-error cost, the stage that takes k_cost's place for
+// a matcher constructed with CostSquareError: one workgroup per item forms
+// CostSquareError::Cost and ComputeGradient's three sums at the item's best
+// sensor pose, which the search left in poses7[0..2] (k_replay, k_match_small),
+// with k_sq_cost_batch's own code (sq_cost_stage.hpp: restated gl_sincos and
+// gl_pow3, term rows, beam-order chains from +0.0) and writes them to
+// costs[0..3] of the item's record, so they reach the host with the record.
+// cp.min_range / cp.max_range hold CostSquareError's beam filter.  Term rows:
+// dynamic LDS where 4 N doubles fit lds_bytes (cost_sq_lds), else the item's
+// global term rows (7 N doubles, of which 4 N are used).
+// --------------------------------------------------------------------------
+__host__ __device__ inline size_t sq_rows_bytes(int n) { return sizeof(double) * (size_t)kSqGradRows * (size_t)n; }
+template <class V>
+inline size_t cost_sq_lds(const V& items)
+{
+    size_t b = 0;
+    for (const auto& it : items)
+        if (sq_rows_bytes(it.cp.N) <= kSqLdsMax) b = std::max(b, sq_rows_bytes(it.cp.N));
+    return b;
+}
+
+__global__ __launch_bounds__(kSqThreads) void k_cost_sq(Items items, unsigned lds_bytes, DevTs dts)
+{
+    const DtsScope dts_scope(dts);
+    const MatchItem& mi = items[blockIdx.x];
+    extern __shared__ double l_rows[];   // [4][N] of the launch's largest in-LDS item
+    __shared__ double s_pose[1][3];
+    __shared__ double s_cost[kSqGradRows];
+    __shared__ int s_err;
+    SqItem it;
+    it.p.min_x = mi.cp.min_x;
+    it.p.min_y = mi.cp.min_y;
+    it.p.res = mi.cp.res;
+    it.p.W = mi.cp.W;
+    it.p.H = mi.cp.H;
+    it.p.N = mi.cp.N;
+    it.p.cost_min = mi.cp.min_range;
+    it.p.cost_max = mi.cp.max_range;
+    it.map = mi.grid;
+    it.ranges = mi.ranges;
+    it.angles = mi.angles;
+    it.rows = mi.terms;
+    const bool in_lds = sq_rows_bytes(it.p.N) <= (size_t)lds_bytes;
+    if (threadIdx.x == 0) {
+        s_pose[0][0] = gload(mi.poses7 + 0);
+        s_pose[0][1] = gload(mi.poses7 + 1);
+        s_pose[0][2] = gload(mi.poses7 + 2);
+        s_err = 0;
+    }
+    __syncthreads();
+    sq_cost_grad(it, s_pose, s_cost, l_rows, in_lds, &s_err);
+    if (threadIdx.x == 0) {
+        RtcsmRecord* rec = mi.rec;
+        for (int k = 0; k < kSqGradRows; ++k) rec->costs[k] = s_cost[k];
+        rec->costs[4] = rec->costs[5] = rec->costs[6] = 0.0;
+        rec->sq_err = s_err;
+    }
+}
+
+// --------------------------------------------------------------------------
 // Small windows: the whole search of a window whose coarse
 // lattice holds ONE block per angle (2 winX < lr and 2 winY < lr: the launcher
 // JSON frontend window, +-0.1 m at 5 cm with LowRes 5) in one launch, one
@@ -4265,6 +4329,7 @@ struct BatchShape {
     bool fine_staged = false;  // ... as k_fine_regs (LowRes 5, every map W even, <= 8192, 16-byte aligned)
     int frows = 1;
     int kernel_size = 0;
+    bool sq = false;        // the cost stage is k_cost_sq (a matcher built with CostSquareError)
     WorkList wl{};          // kept-superblock work list (wl.cnt null: k_coarse_rows)
 };
 
@@ -4700,6 +4765,37 @@ struct ScanOptions {
     bool cost_only = false;
 };
 
+// The cost stage of a batch's n items at the poses the search left in poses7:
+// the greedy-endpoint cost at the 7 poses (k_cost), or, for a matcher built
+// with CostSquareError (B.sq), k_cost_sq alone.
+void enqueue_cost(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::vector<MatchItem>& items, int n,
+                  int inject)
+{
+    hipStream_t st = ctx->stream;
+    double nbeams = 0.0;
+    for (auto& it : items) nbeams += it.cp.N;
+    if (B.sq) {
+        // 5 smoothed values of 16 cells per beam
+        const int tok_ = ctx->timing_begin(K_COST_SQ, 8.0 * 5.0 * 16.0 * nbeams);
+        if (!ctx->skipped(K_COST_SQ)) {
+            const size_t lds = cost_sq_lds(items);
+            sq_allow_lds(k_cost_sq, lds);
+            hipLaunchKernelGGL(k_cost_sq, dim3(n), dim3(kSqThreads), lds, st, d_items, (unsigned)lds, ctx->dts(tok_));
+        }
+        ctx->timing_end(tok_);
+        LGS_HIP_CHECK(hipGetLastError());
+        return;
+    }
+    const double kk = (2.0 * B.kernel_size + 1) * (2.0 * B.kernel_size + 1);
+    const int tok_ = ctx->timing_begin(K_COST, 8.0 * 7.0 * 2.0 * kk * nbeams);
+    if (!ctx->skipped(K_COST))
+        hipLaunchKernelGGL(KCOST(B.kernel_size), dim3(7, n), dim3(kCostThreads), cost_lds(items), st, d_items,
+                           ctx->guard_cap,
+                           ctx->guard_eps, inject, 0, ctx->dts(tok_));
+    ctx->timing_end(tok_);
+    LGS_HIP_CHECK(hipGetLastError());
+}
+
 // Host-patched cost cells (cidx[key.x] = cells, computed on the host with
 // glibc) and the cost terms recomputed from them (k_cost mode 1).
 void enqueue_cost_patches(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::vector<MatchItem>& items,
@@ -4806,16 +4902,7 @@ void enqueue_items(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::
 #undef LGS_SMALL_CASE
         ctx->timing_end(tok);
         LGS_HIP_CHECK(hipGetLastError());
-        const double kk = (2.0 * B.kernel_size + 1) * (2.0 * B.kernel_size + 1);
-        double nbeams = 0.0;
-        for (auto& it : items) nbeams += it.cp.N;
-        const int tok_ = ctx->timing_begin(K_COST, 8.0 * 7.0 * 2.0 * kk * nbeams);
-        if (!ctx->skipped(K_COST))
-            hipLaunchKernelGGL(KCOST(B.kernel_size), dim3(7, n), dim3(kCostThreads), cost_lds(items), st, d_items,
-                               ctx->guard_cap,
-                               ctx->guard_eps, inject, 0, ctx->dts(tok_));
-        ctx->timing_end(tok_);
-        LGS_HIP_CHECK(hipGetLastError());
+        enqueue_cost(ctx, B, d_items, items, n, inject);
         if (opt.cost_patches && !opt.cost_patches->empty())
             enqueue_cost_patches(ctx, B, d_items, items, *opt.cost_patches);
         return;
@@ -5004,19 +5091,8 @@ void enqueue_items(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::
         ctx->timing_end(tok_);
         LGS_HIP_CHECK(hipGetLastError());
     }
-    // cost + covariance terms at the 7 poses
-    const double kk = (2.0 * B.kernel_size + 1) * (2.0 * B.kernel_size + 1);
-    double nbeams = 0.0;
-    for (auto& it : items) nbeams += it.cp.N;
-    {
-        const int tok_ = ctx->timing_begin(K_COST, 8.0 * 7.0 * 2.0 * kk * nbeams);
-        if (!ctx->skipped(K_COST))
-            hipLaunchKernelGGL(KCOST(B.kernel_size), dim3(7, n), dim3(kCostThreads), cost_lds(items), st, d_items,
-                               ctx->guard_cap,
-                               ctx->guard_eps, inject, 0, ctx->dts(tok_));
-        ctx->timing_end(tok_);
-        LGS_HIP_CHECK(hipGetLastError());
-    }
+    // cost + covariance terms at the 7 poses (or the square-error stage)
+    enqueue_cost(ctx, B, d_items, items, n, inject);
     if (opt.cost_patches && !opt.cost_patches->empty())
         enqueue_cost_patches(ctx, B, d_items, items, *opt.cost_patches);
 }
@@ -5161,7 +5237,7 @@ bool check_cost_guards_p7(lgs_ctx* ctx, const double P7[7][3], const CostPlan& c
 }
 
 void finish_summary(const RtcsmPlan& pl, const lgs_scan* scan, lgs_pose2d initial, bool pruned,
-                    const RtcsmRecord& rec, lgs_rtcsm_summary* out)
+                    const RtcsmRecord& rec, lgs_rtcsm_summary* out, bool sq = false)
 {
     std::memset(out, 0, sizeof(*out));
     out->pose_found = rec.found;
@@ -5192,6 +5268,11 @@ void finish_summary(const RtcsmPlan& pl, const lgs_scan* scan, lgs_pose2d initia
     out->covariance[0] += 0.01;
     out->covariance[4] += 0.01;
     out->covariance[8] += 0.01;
+    if (sq) {
+        // k_cost_sq left Cost and ComputeGradient's sums in costs[0..3]
+        // (C/mapping/cost_function_square_error.cpp:112-135)
+        sq_covariance(rec.costs + 1, out->covariance);
+    }
     out->coarse_blocks = pruned ? (int64_t)rec.coarse_evals : pl.K;
     out->fine_blocks = rec.n_eval;
 }
@@ -5214,6 +5295,8 @@ void check_coarse(const lgs_grid* grid, const lgs_grid* coarse)
                 "coarse map must have the fine map's geometry (CreateSameSizeMap)");
 }
 
+const char* const kSqDomainError = "square-error cost: an angle lies outside the restated sincos domain";
+
 // Run n matches as one batch: the items share the search parameters and the
 // map geometry; sets are the distinct coarse maps (set_of[j] = item j's).
 // One host synchronisation in the common case; guarded projections and
@@ -5235,6 +5318,7 @@ struct InFlight {
     bool post = false;            // records written by k_post (LGS_OPT_POST_RECORDS)
     unsigned* flag = nullptr;     // its completion flag in the pinned record buffer
     unsigned post_gen = 0;
+    bool sq_err = false;          // k_cost_sq met an angle outside the restated sincos domain
 };
 
 // Lean projection (LGS_OPT_LEAN_PROJECT): only when every kernel enqueue_items
@@ -5259,7 +5343,7 @@ bool lean_rows(const lgs_ctx* ctx, const BatchShape& B, const std::vector<MatchI
 void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge_params* cost,
                     const lgs_grid* const* grids, lgs_scan* const* scans, const lgs_pose2d* init, int n,
                     double nthr, std::vector<PlaneSet>& sets, const int* set_of, lgs_rtcsm_summary* out,
-                    InFlight& F)
+                    InFlight& F, const lgs_cost_sq_params* sq = nullptr)
 {
     LGS_HIP_CHECK(hipSetDevice(ctx->device));
     LGS_REQUIRE(n >= 1 && n <= kMaxBatchItems, "batch of 1..64 matches (run_chunked splits larger ones)");
@@ -5280,6 +5364,10 @@ void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost
         // the segment prefix of the selection lives in LDS next to the evaluator
         LGS_REQUIRE(it.pl.K <= 7LL * 1024 * 1024, "search window too large (> 7M coarse blocks)");
         it.cp = make_cost_plan(grids[j], cost, scans[j]);
+        if (sq) {   // CostSquareError's beam filter (cost_function_square_error.cpp:27-30)
+            it.cp.min_range = std::max(sq->usable_range_min, scans[j]->min_range);
+            it.cp.max_range = std::min(sq->usable_range_max, scans[j]->max_range);
+        }
         B.Tmax = std::max(B.Tmax, it.pl.T);
         B.NvMax = std::max(B.NvMax, nv);
         Nmax = std::max(Nmax, scans[j]->n);
@@ -5308,6 +5396,7 @@ void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost
         B.fine_staged = grids[j]->w % 2 == 0 && ((uintptr_t)grids[j]->d & 15) == 0 && grids[j]->w <= 8192 &&
                         grids[j]->h <= 8192;
     B.kernel_size = cost->kernel_size;
+    B.sq = sq != nullptr;
     B.nsegMax = (int)(((long long)B.Tmax * B.P + kSelSeg - 1) / kSelSeg);
     // one coarse block per angle: the whole search in one launch, straight
     // from the fine map (no caller-supplied coarse map to honour)
@@ -5533,7 +5622,7 @@ void finish_matches(lgs_ctx* ctx, InFlight& F)
                 rerun = true;
                 slow = 1;
             }
-            if (!rerun && !opt.cost_patches) {
+            if (!rerun && !opt.cost_patches && !B.sq) {
                 const CostPlan& cp = items[j].cp;
                 if (check_cost_guards(ctx, items[j].pl, cp, scans[j], rec, cpatch, full_cost)) {
                     if (full_cost) {
@@ -5580,7 +5669,8 @@ void finish_matches(lgs_ctx* ctx, InFlight& F)
             rec = HostRecord(h_rec[j], g);
             if (opt.patches || opt.host_idx) rec.guard_count = 0;  // already exact
         }
-        finish_summary(items[j].pl, scans[j], init[j], pruned, rec, &out[j]);
+        finish_summary(items[j].pl, scans[j], init[j], pruned, rec, &out[j], B.sq);
+        if (B.sq && rec.sq_err) F.sq_err = true;
         out[j].guard_hits = guard_hits;
         out[j].fixups = fixups;
         out[j].slow_path = slow;
@@ -5595,12 +5685,14 @@ void finish_matches(lgs_ctx* ctx, InFlight& F)
 
 void run_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge_params* cost,
                  const lgs_grid* const* grids, lgs_scan* const* scans, const lgs_pose2d* init, int n,
-                 double nthr, std::vector<PlaneSet>& sets, const int* set_of, lgs_rtcsm_summary* out)
+                 double nthr, std::vector<PlaneSet>& sets, const int* set_of, lgs_rtcsm_summary* out,
+                 const lgs_cost_sq_params* sq = nullptr)
 {
     InFlight F;
     ctx->bank = 0;
-    launch_matches(ctx, params, cost, grids, scans, init, n, nthr, sets, set_of, out, F);
+    launch_matches(ctx, params, cost, grids, scans, init, n, nthr, sets, set_of, out, F, sq);
     finish_matches(ctx, F);
+    if (F.sq_err) throw Error(LGS_ERR_INTERNAL, kSqDomainError);
 }
 
 
@@ -5610,13 +5702,15 @@ constexpr int kMaxBatch = kMaxBatchItems;
 constexpr int kSplitMin = 16;   // smallest chunk of a split call
 void run_chunked(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge_params* cost,
                  const lgs_grid* const* grids, lgs_scan* const* scans, const lgs_pose2d* init, int n,
-                 double nthr, const std::vector<PlaneSet>& sets_all, const int* set_of, lgs_rtcsm_summary* out)
+                 double nthr, const std::vector<PlaneSet>& sets_all, const int* set_of, lgs_rtcsm_summary* out,
+                 const lgs_cost_sq_params* sq = nullptr)
 {
     // two chunks in flight: chunk c + 1 is launched (on the other bank)
     // before the host takes chunk c's results, so the device never waits for
     // the host between chunks of one call
     InFlight fl[2];
     bool busy[2] = { false, false };
+    bool sq_err = false;   // reported once every chunk of the call has finished
     int c = 0;
     // a call of 2 x kSplitMin .. kMaxBatch matches runs as two chunks, so that
     // the two banks overlap even then (an 8-rank shard of the 512-candidate
@@ -5639,23 +5733,26 @@ void run_chunked(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge
             ctx->bank = b;
             fl[b] = InFlight{};
             launch_matches(ctx, params, cost, grids + j0, scans + j0, init + j0, m, nthr, sets, so.data(), out + j0,
-                           fl[b]);
+                           fl[b], sq);
             busy[b] = true;
             if (busy[b ^ 1]) {
                 finish_matches(ctx, fl[b ^ 1]);
                 busy[b ^ 1] = false;
+                sq_err = sq_err || fl[b ^ 1].sq_err;
             }
         }
         const int last = (c - 1) & 1;
         if (busy[last]) {
             finish_matches(ctx, fl[last]);
             busy[last] = false;
+            sq_err = sq_err || fl[last].sq_err;
         }
     } catch (...) {
         ctx->bank = 0;
         throw;
     }
     ctx->bank = 0;
+    if (sq_err) throw Error(LGS_ERR_INTERNAL, kSqDomainError);
 }
 
 }  // namespace
@@ -5858,6 +5955,111 @@ extern "C" int lgs_rtcsm_optimize_pose_query_batch(lgs_ctx* ctx, const lgs_grid*
     });
 }
 
+// ---- the same four with either cost function (lgs_cost_spec).  Kind 0 is the
+// entry point above; kind 1 runs the same search with k_cost_sq as its cost
+// stage, into a buffer of its own so that a failing call writes nothing.
+namespace {
+void check_sq_maps(const lgs_grid* const* grids, int n)
+{
+    for (int j = 0; j < n; ++j)
+        LGS_REQUIRE(grids[j] && (long long)grids[j]->w * grids[j]->h < (1LL << 30),
+                    "square-error cost: null map or map of 2^30 cells or more");
+}
+template <class F>
+int with_own_summaries(lgs_ctx* ctx, lgs_rtcsm_summary* out, int n, F&& f)
+{
+    std::vector<lgs_rtcsm_summary> tmp;
+    const int rc = guarded(ctx, [&] {
+        tmp.resize((size_t)n);
+        f(tmp.data());
+    });
+    if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(lgs_rtcsm_summary) * (size_t)n);
+    return rc;
+}
+}  // namespace
+
+extern "C" int lgs_rtcsm_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* coarse,
+                                                  const lgs_rtcsm_params* params, const lgs_cost_spec* cost,
+                                                  const lgs_scan* const* scans, const lgs_pose2d* initial, int n,
+                                                  double nthr, lgs_rtcsm_summary* out)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq) return lgs_rtcsm_optimize_pose_batch(ctx, grid, coarse, params, sel.ge, scans, initial, n, nthr, out);
+    if (!ctx || !out || !scans || !initial || n < 0 || !grid || !coarse) return LGS_ERR_INVALID_ARG;
+    if (n == 0) return LGS_OK;
+    return with_own_summaries(ctx, out, n, [&](lgs_rtcsm_summary* o) {
+        check_sq_maps(&grid, 1);
+        std::vector<PlaneSet> sets(1);
+        sets[0].coarse = coarse;
+        const std::vector<int> set_of((size_t)n, 0);
+        const std::vector<const lgs_grid*> grids((size_t)n, grid);
+        run_chunked(ctx, params, sel.ge, grids.data(), const_cast<lgs_scan* const*>(scans), initial, n, nthr, sets,
+                    set_of.data(), o, sel.sq);
+    });
+}
+
+extern "C" int lgs_rtcsm_optimize_pose_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* coarse,
+                                            const lgs_rtcsm_params* params, const lgs_cost_spec* cost,
+                                            const lgs_scan* scan, lgs_pose2d initial, double nthr,
+                                            lgs_rtcsm_summary* out)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq) return lgs_rtcsm_optimize_pose(ctx, grid, coarse, params, sel.ge, scan, initial, nthr, out);
+    if (!ctx || !out || !grid || !coarse || !scan) return LGS_ERR_INVALID_ARG;
+    return with_own_summaries(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
+        check_sq_maps(&grid, 1);
+        std::vector<PlaneSet> sets(1);
+        sets[0].coarse = coarse;
+        const int set0 = 0;
+        lgs_scan* s = const_cast<lgs_scan*>(scan);
+        run_matches(ctx, params, sel.ge, &grid, &s, &initial, 1, nthr, sets, &set0, o, sel.sq);
+    });
+}
+
+extern "C" int lgs_rtcsm_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_rtcsm_params* params,
+                                                  const lgs_cost_spec* cost, const lgs_scan* scan,
+                                                  lgs_pose2d initial, lgs_rtcsm_summary* out)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq) return lgs_rtcsm_optimize_pose_query(ctx, grid, params, sel.ge, scan, initial, out);
+    if (!ctx || !grid || !params || !out || !scan) return LGS_ERR_INVALID_ARG;
+    return with_own_summaries(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
+        check_sq_maps(&grid, 1);
+        std::vector<PlaneSet> sets(1);
+        sets[0].fine = grid;
+        const int set0 = 0;
+        lgs_scan* s = const_cast<lgs_scan*>(scan);
+        run_matches(ctx, params, sel.ge, &grid, &s, &initial, 1, DBL_MIN, sets, &set0, o, sel.sq);
+    });
+}
+
+extern "C" int lgs_rtcsm_optimize_pose_query_batch_cost(lgs_ctx* ctx, const lgs_grid* const* grids,
+                                                        const lgs_rtcsm_params* params, const lgs_cost_spec* cost,
+                                                        const lgs_scan* const* scans, const lgs_pose2d* initial,
+                                                        int n, lgs_rtcsm_summary* out)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq) return lgs_rtcsm_optimize_pose_query_batch(ctx, grids, params, sel.ge, scans, initial, n, out);
+    if (!ctx || !grids || !params || !scans || !initial || !out || n < 0) return LGS_ERR_INVALID_ARG;
+    if (n == 0) return LGS_OK;
+    return with_own_summaries(ctx, out, n, [&](lgs_rtcsm_summary* o) {
+        std::vector<PlaneSet> sets((size_t)n);
+        std::vector<int> set_of((size_t)n);
+        for (int j = 0; j < n; ++j) {
+            LGS_REQUIRE(grids[j] && scans[j], "null query");
+            sets[j].fine = grids[j];
+            set_of[j] = j;
+        }
+        check_sq_maps(grids, n);
+        run_chunked(ctx, params, sel.ge, grids, const_cast<lgs_scan* const*>(scans), initial, n, DBL_MIN, sets,
+                    set_of.data(), o, sel.sq);
+    });
+}
+
 extern "C" int lgs_rtcsm_dense_scores(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* coarse,
                                       const lgs_rtcsm_params* params, const lgs_scan* scan,
                                       lgs_pose2d initial, double* coarse_scores,
@@ -5997,11 +6199,11 @@ extern "C" int lgs_cost_greedy_endpoint(lgs_ctx* ctx, const lgs_grid* grid,
 // candidate, in candidate order (found == 0 where the reference appends none).
 // Candidates are independent, so the queries whose local maps share a size
 // are matched together in batches (each query's coarse map built once per batch).
-extern "C" int lgs_loop_detect_rtcsm(lgs_ctx* ctx, const lgs_rtcsm_params* params,
-                                     const lgs_cost_ge_params* cost, double score_threshold,
-                                     const lgs_loop_query* queries, int num_queries,
-                                     const lgs_loop_candidate* candidates, int num_candidates,
-                                     lgs_loop_result* results)
+static int loop_detect_rtcsm_run(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge_params* cost,
+                                 const lgs_cost_sq_params* sq, double score_threshold,
+                                 const lgs_loop_query* queries, int num_queries,
+                                 const lgs_loop_candidate* candidates, int num_candidates,
+                                 lgs_loop_result* results)
 {
     if (!ctx || !params || !cost || (num_queries > 0 && !queries) || num_queries < 0 ||
         num_candidates < 0 || (num_candidates > 0 && (!candidates || !results)))
@@ -6013,6 +6215,8 @@ extern "C" int lgs_loop_detect_rtcsm(lgs_ctx* ctx, const lgs_rtcsm_params* param
         for (int q = 0; q < num_queries; ++q) {
             const lgs_loop_query& Q = queries[q];
             LGS_REQUIRE(Q.map, "loop query without a local map");
+            LGS_REQUIRE(!sq || (long long)Q.map->w * Q.map->h < (1LL << 30),
+                        "square-error cost: map of 2^30 cells or more");
             LGS_REQUIRE(Q.first_candidate == covered && Q.num_candidates >= 0 &&
                             Q.first_candidate + Q.num_candidates <= num_candidates,
                         "loop queries must cover the candidates contiguously and in order");
@@ -6052,7 +6256,7 @@ extern "C" int lgs_loop_detect_rtcsm(lgs_ctx* ctx, const lgs_rtcsm_params* param
             if (cand.empty()) continue;
             std::vector<lgs_rtcsm_summary> sums(cand.size());
             run_chunked(ctx, params, cost, grids.data(), scans.data(), poses.data(), (int)cand.size(),
-                        score_threshold, sets, set_of.data(), sums.data());
+                        score_threshold, sets, set_of.data(), sums.data(), sq);
             for (size_t k = 0; k < cand.size(); ++k) {
                 const int ci = cand[k];
                 int qi = 0;
@@ -6075,6 +6279,37 @@ extern "C" int lgs_loop_detect_rtcsm(lgs_ctx* ctx, const lgs_rtcsm_params* param
             }
         }
     });
+}
+
+extern "C" int lgs_loop_detect_rtcsm(lgs_ctx* ctx, const lgs_rtcsm_params* params,
+                                     const lgs_cost_ge_params* cost, double score_threshold,
+                                     const lgs_loop_query* queries, int num_queries,
+                                     const lgs_loop_candidate* candidates, int num_candidates,
+                                     lgs_loop_result* results)
+{
+    return loop_detect_rtcsm_run(ctx, params, cost, nullptr, score_threshold, queries, num_queries, candidates,
+                                 num_candidates, results);
+}
+
+// With the square-error cost a failing call leaves `results` as it found them.
+extern "C" int lgs_loop_detect_rtcsm_cost(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_spec* cost,
+                                          double score_threshold, const lgs_loop_query* queries, int num_queries,
+                                          const lgs_loop_candidate* candidates, int num_candidates,
+                                          lgs_loop_result* results)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq)
+        return lgs_loop_detect_rtcsm(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
+                                     num_candidates, results);
+    if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
+    std::vector<lgs_loop_result> tmp;
+    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
+    if (rc0 != LGS_OK) return rc0;
+    const int rc = loop_detect_rtcsm_run(ctx, params, sel.ge, sel.sq, score_threshold, queries, num_queries,
+                                         candidates, num_candidates, tmp.data());
+    if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
+    return rc;
 }
 
 namespace {
@@ -6212,18 +6447,19 @@ struct LoopShard {
 
 }  // namespace
 
-extern "C" int lgs_loop_detect_rtcsm_multi(lgs_ctx* const* ctxs, int num_ctx, const lgs_rtcsm_params* params,
-                                           const lgs_cost_ge_params* cost, double score_threshold,
-                                           const lgs_loop_query* queries, int num_queries,
-                                           const lgs_loop_candidate* candidates, int num_candidates,
-                                           lgs_loop_result* results)
+// every shard's detector gets the same cost function (sq null: greedy endpoint)
+static int loop_detect_rtcsm_multi_run(lgs_ctx* const* ctxs, int num_ctx, const lgs_rtcsm_params* params,
+                                       const lgs_cost_ge_params* cost, const lgs_cost_sq_params* sq,
+                                       double score_threshold, const lgs_loop_query* queries, int num_queries,
+                                       const lgs_loop_candidate* candidates, int num_candidates,
+                                       lgs_loop_result* results)
 {
     if (!ctxs || num_ctx < 1 || !ctxs[0]) return LGS_ERR_INVALID_ARG;
     for (int k = 1; k < num_ctx; ++k)
         if (!ctxs[k]) return LGS_ERR_INVALID_ARG;
     lgs_ctx* const c0 = ctxs[0];
     if (num_ctx == 1 || num_candidates <= 1)
-        return lgs_loop_detect_rtcsm(c0, params, cost, score_threshold, queries, num_queries, candidates,
+        return loop_detect_rtcsm_run(c0, params, cost, sq, score_threshold, queries, num_queries, candidates,
                                      num_candidates, results);
     if (!params || !cost || (num_queries > 0 && !queries) || num_queries < 0 || num_candidates < 0 ||
         (num_candidates > 0 && (!candidates || !results)))
@@ -6255,7 +6491,7 @@ extern "C" int lgs_loop_detect_rtcsm_multi(lgs_ctx* const* ctxs, int num_ctx, co
             try {
                 if (hipSetDevice(sh.ctx->device) != hipSuccess) throw Error(LGS_ERR_HIP, "hipSetDevice failed");
                 sh.prepare(queries, num_queries, candidates);
-                sh.status = lgs_loop_detect_rtcsm(sh.ctx, params, cost, score_threshold, sh.qs.data(),
+                sh.status = loop_detect_rtcsm_run(sh.ctx, params, cost, sq, score_threshold, sh.qs.data(),
                                                   (int)sh.qs.size(), sh.cs.data(), (int)sh.cs.size(),
                                                   results + sh.lo);
                 if (sh.status != LGS_OK) sh.error = sh.ctx->last_error;
@@ -6279,6 +6515,38 @@ extern "C" int lgs_loop_detect_rtcsm_multi(lgs_ctx* const* ctxs, int num_ctx, co
         // a result's start_node_index etc. come from its query, which each
         // shard saw clipped but unchanged: nothing to remap
     });
+}
+
+extern "C" int lgs_loop_detect_rtcsm_multi(lgs_ctx* const* ctxs, int num_ctx, const lgs_rtcsm_params* params,
+                                           const lgs_cost_ge_params* cost, double score_threshold,
+                                           const lgs_loop_query* queries, int num_queries,
+                                           const lgs_loop_candidate* candidates, int num_candidates,
+                                           lgs_loop_result* results)
+{
+    return loop_detect_rtcsm_multi_run(ctxs, num_ctx, params, cost, nullptr, score_threshold, queries, num_queries,
+                                       candidates, num_candidates, results);
+}
+
+extern "C" int lgs_loop_detect_rtcsm_multi_cost(lgs_ctx* const* ctxs, int num_ctx, const lgs_rtcsm_params* params,
+                                                const lgs_cost_spec* cost, double score_threshold,
+                                                const lgs_loop_query* queries, int num_queries,
+                                                const lgs_loop_candidate* candidates, int num_candidates,
+                                                lgs_loop_result* results)
+{
+    CostSel sel;
+    if (const int rc = cost_select(cost, &sel)) return rc;
+    if (!sel.sq)
+        return lgs_loop_detect_rtcsm_multi(ctxs, num_ctx, params, sel.ge, score_threshold, queries, num_queries,
+                                           candidates, num_candidates, results);
+    if (!ctxs || num_ctx < 1 || !ctxs[0] || num_candidates < 0 || (num_candidates > 0 && !results))
+        return LGS_ERR_INVALID_ARG;
+    std::vector<lgs_loop_result> tmp;
+    const int rc0 = guarded(ctxs[0], [&] { tmp.resize((size_t)num_candidates); });
+    if (rc0 != LGS_OK) return rc0;
+    const int rc = loop_detect_rtcsm_multi_run(ctxs, num_ctx, params, sel.ge, sel.sq, score_threshold, queries,
+                                               num_queries, candidates, num_candidates, tmp.data());
+    if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
+    return rc;
 }
 
 extern "C" int lgs_debug_offset_checks(lgs_ctx* ctx, int reset, unsigned long long* out)

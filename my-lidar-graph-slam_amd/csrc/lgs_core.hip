@@ -194,7 +194,7 @@ const char* const kKernelNames[K_NUM_KERNELS] = { "k_project", "k_coarse", "k_se
                                                   "k_fine", "k_replay", "k_cost", "k_precompute",
                                                   "k_linsolve", "k_ray_emit", "k_ray_apply",
                                                   "k_super", "k_super_planes", "k_bb_score", "k_bb_expand",
-                                                  "k_coarse_aux", "k_match_small", "k_gs_score" };
+                                                  "k_coarse_aux", "k_match_small", "k_gs_score", "k_cost_sq" };
 }
 
 int lgs_ctx::next_stamp()
@@ -474,6 +474,8 @@ extern "C" int lgs_ctx_kernel_stats(lgs_ctx* ctx, lgs_kernel_stat* out, int cap)
     }
     return n;
 }
+
+extern "C" size_t lgs_cost_spec_size(void) { return sizeof(lgs_cost_spec); }
 
 extern "C" int lgs_ctx_reset_stats(lgs_ctx* ctx)
 {

@@ -115,7 +115,7 @@ struct RtcsmRecord {
     unsigned long long cost_guard_word;
     long long n_eval;     // coarse blocks refined on the fine map
     int best[3];
-    int pad0;
+    int sq_err;           // k_cost_sq: a beam angle left the restated sincos domain
     double score_max;
     double L;             // lower bound used for pruning
     double costs[7];
@@ -253,6 +253,7 @@ enum KernelId { K_PROJECT = 0, K_COARSE, K_SEED, K_SELECT, K_FINE, K_REPLAY, K_C
                 K_COARSE_AUX,   // k_keep + k_unsafe_list: the work-list passes around k_coarse_list
                 K_MATCH_SMALL,  // k_match_small: a small window's whole search (one coarse block per angle)
                 K_GS_SCORE,     // k_gs_score: the grid-search matcher's score + workgroup argmax pass
+                K_COST_SQ,      // k_cost_sq: the correlative pipeline's square-error cost stage
                 K_NUM_KERNELS };
 extern const char* const kKernelNames[K_NUM_KERNELS];
 struct PendingTiming {
@@ -862,6 +863,33 @@ int guarded(lgs_ctx* ctx, F&& f)
         return LGS_ERR_INTERNAL;
     }
 }
+
+// The cost function of a `_cost` entry point: sq is null for the greedy-endpoint
+// cost (ge = &spec->ge), else ge is an all-zero stand-in that no kernel reads.
+struct CostSel {
+    const lgs_cost_ge_params* ge = nullptr;
+    const lgs_cost_sq_params* sq = nullptr;
+};
+// LGS_OK, or LGS_ERR_INVALID_ARG for a null spec, an unknown kind or
+// non-finite square-error ranges (checked before any device work)
+inline int cost_select(const lgs_cost_spec* spec, CostSel* sel)
+{
+    static const lgs_cost_ge_params no_ge = {};
+    if (!spec) return LGS_ERR_INVALID_ARG;
+    if (spec->kind == LGS_COST_GREEDY_ENDPOINT) {
+        sel->ge = &spec->ge;
+        return LGS_OK;
+    }
+    if (spec->kind != LGS_COST_SQUARE_ERROR) return LGS_ERR_INVALID_ARG;
+    if (!std::isfinite(spec->sq.usable_range_min) || !std::isfinite(spec->sq.usable_range_max))
+        return LGS_ERR_INVALID_ARG;
+    sel->ge = &no_ge;
+    sel->sq = &spec->sq;
+    return LGS_OK;
+}
+// k_hc_sq.hip: the square-error cost step of the bb and gs matchers
+void cost_summaries_sq(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_sq_params* cost,
+                       lgs_scan* const* scans, const lgs_pose2d* best, int n, lgs_rtcsm_summary* out);
 
 // f(i) for i in [0, n) on a persistent pool of host threads (at most 16
 // including the caller; at most ceil(n / grain) of them).  f must not throw.

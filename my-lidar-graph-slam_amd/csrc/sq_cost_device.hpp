@@ -1,9 +1,9 @@
 // sq_cost_device.hpp -- the per-beam arithmetic of CostSquareError
 // (C/mapping/cost_function_square_error.cpp: ComputeSmoothedValue :276-346,
-// ComputeMapGradient :172-229) as device functions, shared by k_linsolve.hip
-// and k_hc_sq.hip.  The library is built without relocatable device code, so
-// every translation unit that includes this header compiles its own copy;
-// everything here is forced inline.  DESIGN.md §4.5 has the exactness argument.
+// ComputeMapGradient :172-229) as device functions, shared by k_linsolve.hip,
+// k_hc_sq.hip and (through sq_cost_stage.hpp) k_rtcsm.hip.  The library is
+// built without relocatable device code, so every translation unit that
+// includes this header compiles its own copy; everything here is forced inline.  DESIGN.md §4.5 has the exactness argument.
 #pragma once
 
 #include "lgs_internal.hpp"
@@ -91,7 +91,7 @@ __device__ __forceinline__ double smoothed(const double* __restrict__ g, int W, 
     for (int j = 0; j < 4; ++j) {
         const double* row = g + (size_t)ay.idx[j] * W;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) m[j][i] = row[ax.idx[i]];
+        for (int i = 0; i < 4; ++i) m[j][i] = gload(row + ax.idx[i]);   // global loads, not flat: the map is device memory
     }
     double s = 0.0;
 #pragma unroll

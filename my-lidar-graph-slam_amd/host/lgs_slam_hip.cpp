@@ -164,14 +164,28 @@ static lgs_cost_ge_params ge_of(const CostGreedyEndpointParams& c)
              c.mKernelSize, c.mScalingFactor, c.mStandardDeviation };
 }
 
-// a search matcher constructed with CostSquareError: Cost / NumOfScans() and
-// ComputeCovariance at the best sensor pose replace the search entry point's
-static void apply_cost_sq(const DevicePtr& dev, const lgs_cost_sq_params* cost, const lgs_grid* grid,
-                          const lgs_scan* scan, lgs_rtcsm_summary* summary)
+// a search matcher or loop detector constructed with CostSquareError: the
+// `_cost` entry points evaluate Cost / NumOfScans() and ComputeCovariance at
+// the best sensor pose in the place of the greedy-endpoint cost
+static lgs_cost_spec sq_spec(const lgs_cost_sq_params* cost)
 {
-    if (!cost) return;
-    dev->Check(lgs_summaries_apply_cost_sq(dev->Handle(), &grid, cost, &scan, summary, 1),
-               "lgs_summaries_apply_cost_sq");
+    lgs_cost_spec spec{};
+    spec.kind = LGS_COST_SQUARE_ERROR;
+    spec.sq = *cost;
+    return spec;
+}
+
+// the cost function a loop detector's matcher was constructed with: the
+// reference's detector calls its matcher's OptimizePose, so that cost function
+// produces mEstimatedCovMat (C/mapping/loop_detector_real_time_correlative.cpp:96-125)
+template <class Matcher>
+static lgs_cost_spec spec_of(const Matcher& m)
+{
+    if (m.CostSquareError()) return sq_spec(m.CostSquareError());
+    lgs_cost_spec spec{};
+    spec.kind = LGS_COST_GREEDY_ENDPOINT;
+    spec.ge = m.Cost();
+    return spec;
 }
 
 // ------------------------------------------ ScanMatcherRealTimeCorrelativeHip
@@ -201,10 +215,16 @@ ScanMatcherRealTimeCorrelativeHip::ScanMatcherRealTimeCorrelativeHip(DevicePtr d
 
 ScanMatchingSummary ScanMatcherRealTimeCorrelativeHip::OptimizePose(const ScanMatchingQuery& q)
 {
+    if (CostSquareError()) {
+        const lgs_cost_spec spec = sq_spec(CostSquareError());
+        mDev->Check(lgs_rtcsm_optimize_pose_query_cost(mDev->Handle(), q.mGridMap->Handle(), &mParams, &spec,
+                                                       q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
+                    "lgs_rtcsm_optimize_pose_query_cost");
+        return summary_of(mLast);
+    }
     mDev->Check(lgs_rtcsm_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
                                               q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                 "lgs_rtcsm_optimize_pose_query");
-    apply_cost_sq(mDev, CostSquareError(), q.mGridMap->Handle(), q.mScanData->Handle(), &mLast);
     return summary_of(mLast);
 }
 
@@ -214,10 +234,16 @@ ScanMatchingSummary ScanMatcherRealTimeCorrelativeHip::OptimizePose(const Device
                                                                     const RobotPose2D<double>& initialPose,
                                                                     double thr) const
 {
+    if (CostSquareError()) {
+        const lgs_cost_spec spec = sq_spec(CostSquareError());
+        mDev->Check(lgs_rtcsm_optimize_pose_cost(mDev->Handle(), gridMap.Handle(), precompMap.Handle(), &mParams,
+                                                 &spec, scanData->Handle(), to_c(initialPose), thr, &mLast),
+                    "lgs_rtcsm_optimize_pose_cost");
+        return summary_of(mLast);
+    }
     mDev->Check(lgs_rtcsm_optimize_pose(mDev->Handle(), gridMap.Handle(), precompMap.Handle(), &mParams, &mCost,
                                         scanData->Handle(), to_c(initialPose), thr, &mLast),
                 "lgs_rtcsm_optimize_pose");
-    apply_cost_sq(mDev, CostSquareError(), gridMap.Handle(), scanData->Handle(), &mLast);
     return summary_of(mLast);
 }
 
@@ -254,10 +280,16 @@ ScanMatcherBranchBoundHip::ScanMatcherBranchBoundHip(DevicePtr dev, const ScoreP
 
 ScanMatchingSummary ScanMatcherBranchBoundHip::OptimizePose(const ScanMatchingQuery& q)
 {
+    if (CostSquareError()) {
+        const lgs_cost_spec spec = sq_spec(CostSquareError());
+        mDev->Check(lgs_bb_optimize_pose_query_cost(mDev->Handle(), q.mGridMap->Handle(), &mParams, &spec,
+                                                    q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
+                    "lgs_bb_optimize_pose_query_cost");
+        return summary_of(mLast);
+    }
     mDev->Check(lgs_bb_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
                                            q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                 "lgs_bb_optimize_pose_query");
-    apply_cost_sq(mDev, CostSquareError(), q.mGridMap->Handle(), q.mScanData->Handle(), &mLast);
     return summary_of(mLast);
 }
 
@@ -272,10 +304,16 @@ ScanMatchingSummary ScanMatcherBranchBoundHip::OptimizePose(const DeviceGrid& gr
         throw Error(LGS_ERR_INVALID_ARG, "ScanMatcherBranchBoundHip: one precomputed map per node height needed");
     const lgs_scan* s = scanData->Handle();
     const lgs_pose2d p = to_c(initialPose);
+    if (CostSquareError()) {
+        const lgs_cost_spec spec = sq_spec(CostSquareError());
+        mDev->Check(lgs_bb_optimize_pose_batch_cost(mDev->Handle(), gridMap.Handle(), pyr.data(), &mParams, &spec, &s,
+                                                    &p, 1, thr, &mLast),
+                    "lgs_bb_optimize_pose_batch_cost");
+        return summary_of(mLast);
+    }
     mDev->Check(lgs_bb_optimize_pose_batch(mDev->Handle(), gridMap.Handle(), pyr.data(), &mParams, &mCost, &s, &p,
                                            1, thr, &mLast),
                 "lgs_bb_optimize_pose_batch");
-    apply_cost_sq(mDev, CostSquareError(), gridMap.Handle(), s, &mLast);
     return summary_of(mLast);
 }
 
@@ -317,10 +355,16 @@ ScanMatcherGridSearchHip::ScanMatcherGridSearchHip(DevicePtr dev, const ScorePix
 
 ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const ScanMatchingQuery& q)
 {
+    if (CostSquareError()) {
+        const lgs_cost_spec spec = sq_spec(CostSquareError());
+        mDev->Check(lgs_gs_optimize_pose_query_cost(mDev->Handle(), q.mGridMap->Handle(), &mParams, &spec,
+                                                    q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
+                    "lgs_gs_optimize_pose_query_cost");
+        return summary_of(mLast);
+    }
     mDev->Check(lgs_gs_optimize_pose_query(mDev->Handle(), q.mGridMap->Handle(), &mParams, &mCost,
                                            q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                 "lgs_gs_optimize_pose_query");
-    apply_cost_sq(mDev, CostSquareError(), q.mGridMap->Handle(), q.mScanData->Handle(), &mLast);
     return summary_of(mLast);
 }
 
@@ -329,10 +373,16 @@ ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const DeviceGrid& gri
 {
     const lgs_scan* s = scanData->Handle();
     const lgs_pose2d p = to_c(initialPose);
+    if (CostSquareError()) {
+        const lgs_cost_spec spec = sq_spec(CostSquareError());
+        mDev->Check(lgs_gs_optimize_pose_batch_cost(mDev->Handle(), gridMap.Handle(), &mParams, &spec, &s, &p, 1, thr,
+                                                    &mLast),
+                    "lgs_gs_optimize_pose_batch_cost");
+        return summary_of(mLast);
+    }
     mDev->Check(lgs_gs_optimize_pose_batch(mDev->Handle(), gridMap.Handle(), &mParams, &mCost, &s, &p, 1, thr,
                                            &mLast),
                 "lgs_gs_optimize_pose_batch");
-    apply_cost_sq(mDev, CostSquareError(), gridMap.Handle(), s, &mLast);
     return summary_of(mLast);
 }
 
@@ -572,10 +622,11 @@ void LoopDetectorRealTimeCorrelativeHip::Detect(std::vector<LoopDetectionQuery>&
     std::vector<lgs_loop_result> out(cs.size());
     std::vector<lgs_ctx*> ctxs{ dev->Handle() };
     for (const auto& d : mExtraDevices) ctxs.push_back(d->Handle());
-    dev->Check(lgs_loop_detect_rtcsm_multi(ctxs.data(), (int)ctxs.size(), &mScanMatcher->Params(),
-                                           &mScanMatcher->Cost(), mScoreThreshold, qs.data(), (int)qs.size(),
-                                           cs.data(), (int)cs.size(), out.data()),
-               "lgs_loop_detect_rtcsm_multi");
+    const lgs_cost_spec spec = spec_of(*mScanMatcher);
+    dev->Check(lgs_loop_detect_rtcsm_multi_cost(ctxs.data(), (int)ctxs.size(), &mScanMatcher->Params(), &spec,
+                                                mScoreThreshold, qs.data(), (int)qs.size(), cs.data(),
+                                                (int)cs.size(), out.data()),
+               "lgs_loop_detect_rtcsm_multi_cost");
     for (const auto& r : out) {
         if (!r.found) continue;   // the reference appends only detected loops, in order (:77-88)
         LoopDetectionResult o;
@@ -616,9 +667,10 @@ void LoopDetectorBranchBoundHip::Detect(std::vector<LoopDetectionQuery>& queries
             cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
     }
     std::vector<lgs_loop_result> out(cs.size());
-    dev->Check(lgs_loop_detect_bb(dev->Handle(), &mScanMatcher->Params(), &mScanMatcher->Cost(), mScoreThreshold,
-                                  qs.data(), (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
-               "lgs_loop_detect_bb");
+    const lgs_cost_spec spec = spec_of(*mScanMatcher);
+    dev->Check(lgs_loop_detect_bb_cost(dev->Handle(), &mScanMatcher->Params(), &spec, mScoreThreshold, qs.data(),
+                                       (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
+               "lgs_loop_detect_bb_cost");
     for (const auto& r : out) {
         if (!r.found) continue;   // only detected loops, in query -> node order (:61-84)
         LoopDetectionResult o;
@@ -659,9 +711,10 @@ void LoopDetectorGridSearchHip::Detect(std::vector<LoopDetectionQuery>& queries,
             cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
     }
     std::vector<lgs_loop_result> out(cs.size());
-    dev->Check(lgs_loop_detect_gs(dev->Handle(), &mScanMatcher->Params(), &mScanMatcher->Cost(), mScoreThreshold,
-                                  qs.data(), (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
-               "lgs_loop_detect_gs");
+    const lgs_cost_spec spec = spec_of(*mScanMatcher);
+    dev->Check(lgs_loop_detect_gs_cost(dev->Handle(), &mScanMatcher->Params(), &spec, mScoreThreshold, qs.data(),
+                                       (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
+               "lgs_loop_detect_gs_cost");
     for (const auto& r : out) {
         if (!r.found) continue;   // only detected loops, in query -> node order (:58-80)
         LoopDetectionResult o;

@@ -204,12 +204,13 @@ struct CostGreedyEndpointParams {
 // launcher's CreateCostFunction (C/slam_launcher.cpp:96-107) gives a matcher
 // either cost; every matcher below has a constructor for each.  A search
 // matcher (correlative, branch-and-bound, grid search) constructed with this
-// one runs its search as ever and then evaluates Cost and ComputeCovariance
-// of this cost at the best sensor pose, as the reference does
-// (lgs_summaries_apply_cost_sq); the search entry point's own
-// greedy-endpoint cost, evaluated with the default parameters, is overwritten.
-// The loop detectors read only Params() and Cost() of their matcher: they
-// stay greedy-endpoint.
+// one runs its search as ever and evaluates Cost and ComputeCovariance of
+// this cost at the best sensor pose, as the reference does, in the place of
+// the greedy-endpoint cost (the `_cost` entry points with
+// LGS_COST_SQUARE_ERROR; the correlative matcher as a stage of its pipeline).
+// A loop detector uses the cost function of the matcher it is given
+// (matcher->CostSquareError() when non-null, else Cost()), so its loop edges'
+// mEstimatedCovMat is that cost function's, as in the reference.
 struct CostSquareErrorParams {
     double mUsableRangeMin = 0.01, mUsableRangeMax = 20.0;
 };

@@ -50,7 +50,8 @@ LGS_OPT_PGCG_GRID_NODES = 36  # lgs_pg_cg_solve: node count from which the solve
 LGS_OPT_FAST_ROWS = 37       # lean batches: certified fast hit-point cells in the superblock pass (0: exact chain)
 KERNEL_IDS = ["k_project", "k_coarse", "k_seed", "k_select", "k_fine", "k_replay", "k_cost", "k_precompute",
               "k_linsolve", "k_ray_emit", "k_ray_apply", "k_super", "k_super_planes", "k_bb_score",
-              "k_bb_expand", "k_coarse_aux", "k_match_small", "k_gs_score"]   # lgs_ctx_kernel_stats order
+              "k_bb_expand", "k_coarse_aux", "k_match_small", "k_gs_score",
+              "k_cost_sq"]   # lgs_ctx_kernel_stats order
 
 
 class Pose2D(C.Structure):
@@ -149,6 +150,31 @@ class HCSummary(C.Structure):
 class CostSQParams(C.Structure):
     """lgs_cost_sq_params: CostSquareError ctor (usableRangeMin, usableRangeMax)."""
     _fields_ = [("usable_range_min", C.c_double), ("usable_range_max", C.c_double)]
+
+
+LGS_COST_GREEDY_ENDPOINT = 0
+LGS_COST_SQUARE_ERROR = 1
+
+
+class CostSpec(C.Structure):
+    """lgs_cost_spec: the cost function of a `_cost` entry point (kind selects ge or sq)."""
+    _fields_ = [("kind", C.c_int), ("ge", CostGEParams), ("sq", CostSQParams)]
+
+
+def cost_spec(cost) -> "CostSpec":
+    """the CostSpec of a CostGEParams or a CostSQParams"""
+    if isinstance(cost, CostSpec):
+        return cost
+    if isinstance(cost, CostSQParams):
+        return CostSpec(LGS_COST_SQUARE_ERROR, CostGEParams(), cost)
+    if isinstance(cost, CostGEParams):
+        return CostSpec(LGS_COST_GREEDY_ENDPOINT, cost, CostSQParams())
+    raise TypeError(f"cost must be CostGEParams, CostSQParams or CostSpec, not {type(cost).__name__}")
+
+
+def _is_ge(cost) -> bool:
+    """a CostGEParams keeps calling the greedy-endpoint entry points"""
+    return isinstance(cost, CostGEParams)
 
 
 class BuilderParams(C.Structure):
@@ -326,6 +352,39 @@ _PROTOS = [
     ("lgs_loop_detect_rtcsm_multi", C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(RtcsmParams),
                                               C.POINTER(CostGEParams), C.c_double, C.POINTER(LoopQuery), C.c_int,
                                               C.POINTER(LoopCandidate), C.c_int, C.POINTER(LoopResult)]),
+    ("lgs_cost_spec_size", C.c_size_t, []),
+    ("lgs_rtcsm_optimize_pose_cost", C.c_int, [_P, _P, _P, C.POINTER(RtcsmParams), C.POINTER(CostSpec), _P,
+                                               Pose2D, C.c_double, C.POINTER(RtcsmSummary)]),
+    ("lgs_rtcsm_optimize_pose_query_cost", C.c_int, [_P, _P, C.POINTER(RtcsmParams), C.POINTER(CostSpec), _P,
+                                                     Pose2D, C.POINTER(RtcsmSummary)]),
+    ("lgs_rtcsm_optimize_pose_query_batch_cost", C.c_int, [_P, C.POINTER(_P), C.POINTER(RtcsmParams),
+                                                           C.POINTER(CostSpec), C.POINTER(_P), C.POINTER(Pose2D),
+                                                           C.c_int, C.POINTER(RtcsmSummary)]),
+    ("lgs_rtcsm_optimize_pose_batch_cost", C.c_int, [_P, _P, _P, C.POINTER(RtcsmParams), C.POINTER(CostSpec),
+                                                     C.POINTER(_P), C.POINTER(Pose2D), C.c_int, C.c_double,
+                                                     C.POINTER(RtcsmSummary)]),
+    ("lgs_bb_optimize_pose_batch_cost", C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(BBParams), C.POINTER(CostSpec),
+                                                  C.POINTER(_P), C.POINTER(Pose2D), C.c_int, C.c_double,
+                                                  C.POINTER(RtcsmSummary)]),
+    ("lgs_bb_optimize_pose_query_cost", C.c_int, [_P, _P, C.POINTER(BBParams), C.POINTER(CostSpec), _P, Pose2D,
+                                                  C.POINTER(RtcsmSummary)]),
+    ("lgs_gs_optimize_pose_batch_cost", C.c_int, [_P, _P, C.POINTER(GSParams), C.POINTER(CostSpec), C.POINTER(_P),
+                                                  C.POINTER(Pose2D), C.c_int, C.c_double,
+                                                  C.POINTER(RtcsmSummary)]),
+    ("lgs_gs_optimize_pose_query_cost", C.c_int, [_P, _P, C.POINTER(GSParams), C.POINTER(CostSpec), _P, Pose2D,
+                                                  C.POINTER(RtcsmSummary)]),
+    ("lgs_loop_detect_rtcsm_cost", C.c_int, [_P, C.POINTER(RtcsmParams), C.POINTER(CostSpec), C.c_double,
+                                             C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
+                                             C.POINTER(LoopResult)]),
+    ("lgs_loop_detect_rtcsm_multi_cost", C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(RtcsmParams),
+                                                   C.POINTER(CostSpec), C.c_double, C.POINTER(LoopQuery), C.c_int,
+                                                   C.POINTER(LoopCandidate), C.c_int, C.POINTER(LoopResult)]),
+    ("lgs_loop_detect_bb_cost", C.c_int, [_P, C.POINTER(BBParams), C.POINTER(CostSpec), C.c_double,
+                                          C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
+                                          C.POINTER(LoopResult)]),
+    ("lgs_loop_detect_gs_cost", C.c_int, [_P, C.POINTER(GSParams), C.POINTER(CostSpec), C.c_double,
+                                          C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
+                                          C.POINTER(LoopResult)]),
     ("lgs_loop_shard_bounds", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("lgs_loop_records_allgather", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(LoopResult),
                                              C.POINTER(LoopResult)]),
@@ -444,7 +503,9 @@ class Context:
     def check(self, rc: int, what: str):
         if rc != LGS_OK:
             msg = self.lib.lgs_ctx_last_error(self.h)
-            raise LgsError(f"{what}: status {rc}: {msg.decode() if msg else ''}")
+            err = LgsError(f"{what}: status {rc}: {msg.decode() if msg else ''}")
+            err.status = rc   # the LGS_ERR_* code
+            raise err
 
     def set_option(self, opt: int, value: float):
         self.check(self.lib.lgs_ctx_set_option(self.h, opt, float(value)), "set_option")
@@ -546,7 +607,15 @@ class Context:
     # ---- matcher ----
     def optimize_pose(self, grid, coarse, params: RtcsmParams, cost: CostGEParams, scan, init,
                       thr: float) -> RtcsmSummary:
+        """cost: a CostGEParams (the greedy-endpoint entry point) or a CostSQParams / CostSpec (its `_cost` twin);
+        the same holds for every matcher and loop-detector method below"""
         out = RtcsmSummary()
+        if not _is_ge(cost):
+            rc = self.lib.lgs_rtcsm_optimize_pose_cost(self.h, grid.h, coarse.h, C.byref(params),
+                                                       C.byref(cost_spec(cost)), scan.h, Pose2D(*init), float(thr),
+                                                       C.byref(out))
+            self.check(rc, "rtcsm_optimize_pose_cost")
+            return out
         rc = self.lib.lgs_rtcsm_optimize_pose(self.h, grid.h, coarse.h, C.byref(params), C.byref(cost), scan.h,
                                               Pose2D(*init), float(thr), C.byref(out))
         self.check(rc, "rtcsm_optimize_pose")
@@ -554,6 +623,11 @@ class Context:
 
     def optimize_pose_query(self, grid, params: RtcsmParams, cost: CostGEParams, scan, init) -> RtcsmSummary:
         out = RtcsmSummary()
+        if not _is_ge(cost):
+            rc = self.lib.lgs_rtcsm_optimize_pose_query_cost(self.h, grid.h, C.byref(params), C.byref(cost_spec(cost)),
+                                                             scan.h, Pose2D(*init), C.byref(out))
+            self.check(rc, "rtcsm_optimize_pose_query_cost")
+            return out
         rc = self.lib.lgs_rtcsm_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
                                                     Pose2D(*init), C.byref(out))
         self.check(rc, "rtcsm_optimize_pose_query")
@@ -569,6 +643,11 @@ class Context:
         sarr = (_P * n)(*[s.h for s in scans])
         poses = (Pose2D * n)(*[Pose2D(*p) for p in inits])
         out = (RtcsmSummary * n)()
+        if not _is_ge(cost):
+            rc = self.lib.lgs_rtcsm_optimize_pose_query_batch_cost(self.h, garr, C.byref(params),
+                                                                   C.byref(cost_spec(cost)), sarr, poses, n, out)
+            self.check(rc, "rtcsm_optimize_pose_query_batch_cost")
+            return list(out)
         rc = self.lib.lgs_rtcsm_optimize_pose_query_batch(self.h, garr, C.byref(params), C.byref(cost), sarr,
                                                           poses, n, out)
         self.check(rc, "rtcsm_optimize_pose_query_batch")
@@ -579,6 +658,11 @@ class Context:
         arr = (_P * n)(*[s.h for s in scans])
         poses = (Pose2D * n)(*[Pose2D(*p) for p in inits])
         out = (RtcsmSummary * n)()
+        if not _is_ge(cost):
+            rc = self.lib.lgs_rtcsm_optimize_pose_batch_cost(self.h, grid.h, coarse.h, C.byref(params),
+                                                             C.byref(cost_spec(cost)), arr, poses, n, float(thr), out)
+            self.check(rc, "rtcsm_optimize_pose_batch_cost")
+            return list(out)
         rc = self.lib.lgs_rtcsm_optimize_pose_batch(self.h, grid.h, coarse.h, C.byref(params), C.byref(cost),
                                                     arr, poses, n, float(thr), out)
         self.check(rc, "rtcsm_optimize_pose_batch")
@@ -612,9 +696,20 @@ class Context:
         out = (LoopResult * max(1, len(candidates)))()
         if shards:
             hs = (_P * (1 + len(shards)))(self.h, *[c.h for c in shards])
+            if not _is_ge(cost):
+                self.check(self.lib.lgs_loop_detect_rtcsm_multi_cost(hs, len(hs), C.byref(params),
+                                                                     C.byref(cost_spec(cost)), float(thr), qs,
+                                                                     len(queries), cs, len(candidates), out),
+                           "loop_detect_rtcsm_multi_cost")
+                return out
             self.check(self.lib.lgs_loop_detect_rtcsm_multi(hs, len(hs), C.byref(params), C.byref(cost), float(thr),
                                                             qs, len(queries), cs, len(candidates), out),
                        "loop_detect_rtcsm_multi")
+            return out
+        if not _is_ge(cost):
+            self.check(self.lib.lgs_loop_detect_rtcsm_cost(self.h, C.byref(params), C.byref(cost_spec(cost)), float(thr),
+                                                           qs, len(queries), cs, len(candidates), out),
+                       "loop_detect_rtcsm_cost")
             return out
         self.check(self.lib.lgs_loop_detect_rtcsm(self.h, C.byref(params), C.byref(cost), float(thr), qs,
                                                   len(queries), cs, len(candidates), out), "loop_detect_rtcsm")
@@ -662,12 +757,22 @@ class Context:
         sarr = (_P * n)(*[s.h for s in scans])
         poses = (Pose2D * n)(*[Pose2D(*p) for p in inits])
         out = (RtcsmSummary * max(1, n))()
+        if not _is_ge(cost):
+            self.check(self.lib.lgs_bb_optimize_pose_batch_cost(self.h, grid.h, parr, C.byref(params),
+                                                                C.byref(cost_spec(cost)), sarr, poses, n, float(thr),
+                                                                out), "bb_optimize_pose_batch_cost")
+            return list(out)[:n]
         self.check(self.lib.lgs_bb_optimize_pose_batch(self.h, grid.h, parr, C.byref(params), C.byref(cost), sarr,
                                                        poses, n, float(thr), out), "bb_optimize_pose_batch")
         return list(out)[:n]
 
     def bb_optimize_pose_query(self, grid, params: "BBParams", cost: CostGEParams, scan, init) -> RtcsmSummary:
         out = RtcsmSummary()
+        if not _is_ge(cost):
+            self.check(self.lib.lgs_bb_optimize_pose_query_cost(self.h, grid.h, C.byref(params),
+                                                                C.byref(cost_spec(cost)), scan.h, Pose2D(*init),
+                                                                C.byref(out)), "bb_optimize_pose_query_cost")
+            return out
         self.check(self.lib.lgs_bb_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
                                                        Pose2D(*init), C.byref(out)), "bb_optimize_pose_query")
         return out
@@ -681,6 +786,10 @@ class Context:
         for i, (s, pose, idx) in enumerate(candidates):
             cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
         out = (LoopResult * max(1, len(candidates)))()
+        if not _is_ge(cost):
+            self.check(self.lib.lgs_loop_detect_bb_cost(self.h, C.byref(params), C.byref(cost_spec(cost)), float(thr), qs,
+                                                        len(queries), cs, len(candidates), out), "loop_detect_bb_cost")
+            return out
         self.check(self.lib.lgs_loop_detect_bb(self.h, C.byref(params), C.byref(cost), float(thr), qs,
                                                len(queries), cs, len(candidates), out), "loop_detect_bb")
         return out
@@ -691,12 +800,22 @@ class Context:
         sarr = (_P * max(1, n))(*[s.h for s in scans])
         poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in inits])
         out = (RtcsmSummary * max(1, n))()
+        if not _is_ge(cost):
+            self.check(self.lib.lgs_gs_optimize_pose_batch_cost(self.h, grid.h, C.byref(params),
+                                                                C.byref(cost_spec(cost)), sarr, poses, n, float(thr),
+                                                                out), "gs_optimize_pose_batch_cost")
+            return list(out)[:n]
         self.check(self.lib.lgs_gs_optimize_pose_batch(self.h, grid.h, C.byref(params), C.byref(cost), sarr, poses,
                                                        n, float(thr), out), "gs_optimize_pose_batch")
         return list(out)[:n]
 
     def gs_optimize_pose_query(self, grid, params: "GSParams", cost: CostGEParams, scan, init) -> RtcsmSummary:
         out = RtcsmSummary()
+        if not _is_ge(cost):
+            self.check(self.lib.lgs_gs_optimize_pose_query_cost(self.h, grid.h, C.byref(params),
+                                                                C.byref(cost_spec(cost)), scan.h, Pose2D(*init),
+                                                                C.byref(out)), "gs_optimize_pose_query_cost")
+            return out
         self.check(self.lib.lgs_gs_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
                                                        Pose2D(*init), C.byref(out)), "gs_optimize_pose_query")
         return out
@@ -720,6 +839,10 @@ class Context:
         for i, (s, pose, idx) in enumerate(candidates):
             cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
         out = (LoopResult * max(1, len(candidates)))()
+        if not _is_ge(cost):
+            self.check(self.lib.lgs_loop_detect_gs_cost(self.h, C.byref(params), C.byref(cost_spec(cost)), float(thr), qs,
+                                                        len(queries), cs, len(candidates), out), "loop_detect_gs_cost")
+            return out
         self.check(self.lib.lgs_loop_detect_gs(self.h, C.byref(params), C.byref(cost), float(thr), qs,
                                                len(queries), cs, len(candidates), out), "loop_detect_gs")
         return out

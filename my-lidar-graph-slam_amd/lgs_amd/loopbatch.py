@@ -74,9 +74,12 @@ def sub_queries(cands: Sequence[Candidate], lo: int, hi: int) -> List[Tuple[int,
 
 
 def hip_detect_fn(ctx: "abi.Context", maps: Sequence[LocalMap], cands: Sequence[Candidate],
-                  params: "abi.RtcsmParams", cost: "abi.CostGEParams", threshold: float
+                  params: "abi.RtcsmParams", cost, threshold: float
                   ) -> Callable[[List[Tuple[int, int, int]], int, int], np.ndarray]:
-    """Per-rank matcher on the GPU: uploads the maps its block needs once."""
+    """Per-rank matcher on the GPU: uploads the maps its block needs once.
+    cost: the detector's matcher's cost function, a CostGEParams or a CostSQParams
+    (the records' normalized_cost and covariance are then CostSquareError's); the
+    same holds for hip_detect_fn_bb and hip_detect_fn_gs."""
     grids = {}
     scans = {}
 
@@ -101,7 +104,7 @@ def hip_detect_fn(ctx: "abi.Context", maps: Sequence[LocalMap], cands: Sequence[
 
 
 def hip_detect_fn_bb(ctx: "abi.Context", maps: Sequence[LocalMap], cands: Sequence[Candidate],
-                     params: "abi.BBParams", cost: "abi.CostGEParams", threshold: float
+                     params: "abi.BBParams", cost, threshold: float
                      ) -> Callable[[List[Tuple[int, int, int]], int, int], np.ndarray]:
     """As hip_detect_fn with LoopDetectorBranchBound (C/mapping/loop_detector_branch_bound.cpp:26-117):
     lgs_loop_detect_bb builds each query's map pyramid itself."""
@@ -127,7 +130,7 @@ def hip_detect_fn_bb(ctx: "abi.Context", maps: Sequence[LocalMap], cands: Sequen
 
 
 def hip_detect_fn_gs(ctx: "abi.Context", maps: Sequence[LocalMap], cands: Sequence[Candidate],
-                     params: "abi.GSParams", cost: "abi.CostGEParams", threshold: float
+                     params: "abi.GSParams", cost, threshold: float
                      ) -> Callable[[List[Tuple[int, int, int]], int, int], np.ndarray]:
     """As hip_detect_fn with LoopDetectorGridSearch (C/mapping/loop_detector_grid_search.cpp:26-106):
     lgs_loop_detect_gs needs nothing precomputed per map."""
