@@ -17,6 +17,7 @@ oracle_ref:
 
 cpptest: host oracle
 	$(MAKE) -C tests/cpp
+	$(MAKE) -C tests/cpp_ge_exact
 	$(MAKE) -C tests/cpp_gs
 	$(MAKE) -C tests/cpp_hc
 	$(MAKE) -C tests/cpp_hc_sq
@@ -30,6 +31,7 @@ clean:
 	$(MAKE) -C oracle clean
 	$(MAKE) -C oracle/ref clean
 	$(MAKE) -C tests/cpp clean
+	$(MAKE) -C tests/cpp_ge_exact clean
 	$(MAKE) -C tests/cpp_gs clean
 	$(MAKE) -C tests/cpp_hc clean
 	$(MAKE) -C tests/cpp_hc_sq clean

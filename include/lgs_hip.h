@@ -807,6 +807,24 @@ int  lgs_cost_square_error_batch(lgs_ctx* ctx, const lgs_grid* const* grids, con
 int  lgs_summaries_apply_cost_sq(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_sq_params* cost,
                                  const lgs_scan* const* scans, lgs_rtcsm_summary* summaries, int n);
 
+/* ---- the greedy-endpoint cost bit for bit, for the search matchers ----
+ * Item j: CostGreedyEndpoint::Cost (cost_function_greedy_endpoint.cpp:32-111) at sensor_poses[j]
+ * on grids[j] with scans[j] and, if out_covariance != NULL, ComputeCovariance (:114-171) there
+ * (the six central-difference costs in the same launch, the covariance formed on the host in the
+ * reference's expression order).  Pointers may repeat; grids may differ in size and resolution
+ * (one term table per distinct resolution, cached on the context).  One launch per chunk (4096
+ * items), one synchronisation per call.  Equal to n calls of lgs_cost_ge_exact at the seven
+ * poses byte for byte.  Caps and status codes of lgs_cost_ge_exact; a failing call writes
+ * nothing. */
+int  lgs_cost_ge_exact_batch(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_ge_params* cost,
+                             const lgs_scan* const* scans, const lgs_pose2d* sensor_poses, int n,
+                             double* out_cost /* n */, double* out_covariance /* 9 n or NULL */);
+/* summaries[j].normalized_cost = Cost(best_sensor_pose) / NumOfScans() and .covariance =
+ * ComputeCovariance(best_sensor_pose), both the reference's bytes; every other field is left as
+ * it is.  What LGS_COST_GREEDY_ENDPOINT_EXACT gives through the `_cost` entry points below. */
+int  lgs_summaries_apply_cost_ge_exact(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_ge_params* cost,
+                                       const lgs_scan* const* scans, lgs_rtcsm_summary* summaries, int n);
+
 /* ScanMatcherHillClimbing with CostSquareError: the contracts, caps and status
  * codes of the lgs_hc_* trio (kernel size and standard deviation apart), plus
  * finite usable ranges.  lgs_hc_summary is reused with two differences:
@@ -839,16 +857,32 @@ int  lgs_hc_sq_trace(lgs_ctx* ctx, const lgs_grid* grid, const lgs_hc_params* pa
  *     pipeline, at the best pose the search left on the device (k_cost_sq: no
  *     greedy-endpoint stage, no second synchronisation); the branch-and-bound
  *     and grid-search matchers run one k_sq_cost_batch launch per call.
- * An unknown kind or non-finite usable ranges: LGS_ERR_INVALID_ARG before any
- * device work.  The caps and status codes of lgs_cost_square_error_batch
- * apply (a map of 2^30 cells or more: LGS_ERR_INVALID_ARG; an angle outside
- * the restated sincos domain: LGS_ERR_INTERNAL); with kind 1 a failing call
- * writes nothing to `out` / `results`. */
+ *   kind == LGS_COST_GREEDY_ENDPOINT_EXACT  the greedy-endpoint cost of
+ *     spec->ge bit for bit: normalized_cost = CostGreedyEndpoint::Cost(
+ *     best_sensor_pose) / NumOfScans() and covariance = ComputeCovariance(
+ *     best_sensor_pose) with the reference's bytes, whether or not a pose was
+ *     found (as lgs_summaries_apply_cost_ge_exact gives); kind 0 holds both to
+ *     1e-5 only.  Every other summary field and every other byte of a loop
+ *     record is kind 0's, except guard_hits and fixups as for kind 1.  The
+ *     correlative matcher runs the stage k_cost_gx in k_cost's place (the
+ *     hill-climbing cost's code: restated sincos, table terms, beam-order
+ *     sums; no guard records, no host fix-up); the branch-and-bound and
+ *     grid-search matchers run one k_ge_cost_batch launch per chunk.  The
+ *     hill-climbing cost's caps apply: kernel_size in [0, 16], standard
+ *     deviation and map resolution finite and > 0, maps of fewer than 2^30
+ *     cells, scans of at least one beam.
+ * An unknown kind, non-finite usable ranges or a kind-2 cost beyond its caps:
+ * LGS_ERR_INVALID_ARG before any device work.  The caps and status codes of
+ * lgs_cost_square_error_batch apply to kind 1 (a map of 2^30 cells or more:
+ * LGS_ERR_INVALID_ARG); an angle outside the restated sincos domain fails a
+ * kind-1 or kind-2 call with LGS_ERR_INTERNAL; with kinds 1 and 2 a failing
+ * call writes nothing to `out` / `results`. */
 #define LGS_COST_GREEDY_ENDPOINT 0
 #define LGS_COST_SQUARE_ERROR    1
+#define LGS_COST_GREEDY_ENDPOINT_EXACT 2   /* reads spec->ge */
 typedef struct {
     int kind;                 /* LGS_COST_* */
-    lgs_cost_ge_params ge;    /* read when kind == 0 */
+    lgs_cost_ge_params ge;    /* read when kind == 0 or 2 */
     lgs_cost_sq_params sq;    /* read when kind == 1 */
 } lgs_cost_spec;
 size_t lgs_cost_spec_size(void);   /* sizeof(lgs_cost_spec), for bindings */

@@ -483,7 +483,7 @@ struct BBLevel {
 // first descent changed the threshold the superset was built with).
 void run_bb(lgs_ctx* ctx, const lgs_bb_params* p, const lgs_cost_ge_params* cost, const lgs_grid* const* grids,
             const double* const* const* pyr, lgs_scan* const* scans, const lgs_pose2d* init, int n, double nthr,
-            lgs_rtcsm_summary* out, bool no_path = false, const lgs_cost_sq_params* sq = nullptr)
+            lgs_rtcsm_summary* out, bool no_path = false, CostAlt alt = {})
 {
     for (int k = 0; k < n; ++k) grid_acquire(ctx, grids[k]);
     LGS_HIP_CHECK(hipSetDevice(ctx->device));
@@ -878,8 +878,8 @@ void run_bb(lgs_ctx* ctx, const lgs_bb_params* p, const lgs_cost_ge_params* cost
     // cost and covariance at the best poses (:146-153), grouped by map
     std::vector<int> order, redo;
     for (int j = 0; j < n; ++j) (failed[(size_t)j] ? redo : order).push_back(j);
-    if (sq) {
-        // CostSquareError: one launch over every item, whatever its map
+    if (alt) {
+        // CostSquareError or the exact greedy-endpoint cost: one launch over every item, whatever its map
         std::vector<const lgs_grid*> gs;
         std::vector<lgs_scan*> sc;
         std::vector<lgs_pose2d> bp;
@@ -890,7 +890,10 @@ void run_bb(lgs_ctx* ctx, const lgs_bb_params* p, const lgs_cost_ge_params* cost
             bp.push_back(best[j]);
             tmp.push_back(out[j]);
         }
-        cost_summaries_sq(ctx, gs.data(), sq, sc.data(), bp.data(), (int)order.size(), tmp.data());
+        if (alt.sq)
+            cost_summaries_sq(ctx, gs.data(), alt.sq, sc.data(), bp.data(), (int)order.size(), tmp.data());
+        else
+            cost_summaries_gx(ctx, gs.data(), cost, sc.data(), bp.data(), (int)order.size(), tmp.data());
         for (size_t k = 0; k < order.size(); ++k) out[order[k]] = tmp[k];
         order.clear();
     }
@@ -929,7 +932,7 @@ void run_bb(lgs_ctx* ctx, const lgs_bb_params* p, const lgs_cost_ge_params* cost
             i2.push_back(init[j]);
         }
         std::vector<lgs_rtcsm_summary> o2(redo.size());
-        run_bb(ctx, p, cost, g2.data(), p2.data(), s2.data(), i2.data(), (int)redo.size(), nthr, o2.data(), true, sq);
+        run_bb(ctx, p, cost, g2.data(), p2.data(), s2.data(), i2.data(), (int)redo.size(), nthr, o2.data(), true, alt);
         for (size_t k = 0; k < redo.size(); ++k) out[redo[k]] = o2[k];
     }
 }
@@ -979,9 +982,9 @@ extern "C" int lgs_grid_precompute_pyramid(lgs_ctx* ctx, const lgs_grid* in, int
     });
 }
 
-// sq non-null: the cost step is CostSquareError's (k_sq_cost_batch)
+// alt: the cost step is CostSquareError's (k_sq_cost_batch) or the exact greedy-endpoint one (k_ge_cost_batch)
 static int bb_batch_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* const* pyramid,
-                        const lgs_bb_params* params, const lgs_cost_ge_params* cost, const lgs_cost_sq_params* sq,
+                        const lgs_bb_params* params, const lgs_cost_ge_params* cost, CostAlt alt,
                         const lgs_scan* const* scans, const lgs_pose2d* initial, int n, double nthr,
                         lgs_rtcsm_summary* out)
 {
@@ -989,7 +992,7 @@ static int bb_batch_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* cons
     if (n == 0) return LGS_OK;
     return guarded(ctx, [&] {
         check_bb(params, cost);
-        LGS_REQUIRE(!sq || (long long)grid->w * grid->h < (1LL << 30), "square-error cost: map of 2^30 cells or more");
+        LGS_REQUIRE(!alt || (long long)grid->w * grid->h < (1LL << 30), "square-error or exact cost: map of 2^30 cells or more");
         std::vector<const double*> pyr;
         for (int h = 0; h <= params->node_height_max; ++h) {
             LGS_REQUIRE(pyramid[h] && pyramid[h]->w == grid->w && pyramid[h]->h == grid->h,
@@ -1006,7 +1009,7 @@ static int bb_batch_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* cons
         for (int j0 = 0; j0 < n; j0 += kBBBatch) {
             const int m = std::min(kBBBatch, n - j0);
             run_bb(ctx, params, cost, grids.data() + j0, pp.data() + j0, sc.data() + j0, initial + j0, m, nthr,
-                   out + j0, false, sq);
+                   out + j0, false, alt);
         }
     });
 }
@@ -1016,7 +1019,7 @@ extern "C" int lgs_bb_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, co
                                           const lgs_scan* const* scans, const lgs_pose2d* initial, int n,
                                           double nthr, lgs_rtcsm_summary* out)
 {
-    return bb_batch_run(ctx, grid, pyramid, params, cost, nullptr, scans, initial, n, nthr, out);
+    return bb_batch_run(ctx, grid, pyramid, params, cost, CostAlt{}, scans, initial, n, nthr, out);
 }
 
 // With the square-error cost a failing call leaves `out` as it found it.
@@ -1027,29 +1030,29 @@ extern "C" int lgs_bb_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* gri
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq) return lgs_bb_optimize_pose_batch(ctx, grid, pyramid, params, sel.ge, scans, initial, n, nthr, out);
+    if (!sel.alt) return lgs_bb_optimize_pose_batch(ctx, grid, pyramid, params, sel.ge, scans, initial, n, nthr, out);
     if (!out || n < 0) return LGS_ERR_INVALID_ARG;
     std::vector<lgs_rtcsm_summary> tmp;
     const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)n); });
     if (rc0 != LGS_OK) return rc0;
-    const int rc = bb_batch_run(ctx, grid, pyramid, params, sel.ge, sel.sq, scans, initial, n, nthr, tmp.data());
+    const int rc = bb_batch_run(ctx, grid, pyramid, params, sel.ge, sel.alt, scans, initial, n, nthr, tmp.data());
     if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(lgs_rtcsm_summary) * (size_t)n);
     return rc;
 }
 
 static int bb_query_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_bb_params* params,
-                        const lgs_cost_ge_params* cost, const lgs_cost_sq_params* sq, const lgs_scan* scan,
+                        const lgs_cost_ge_params* cost, CostAlt alt, const lgs_scan* scan,
                         lgs_pose2d initial, lgs_rtcsm_summary* out)
 {
     if (!ctx || !grid || !scan || !out) return LGS_ERR_INVALID_ARG;
     return guarded(ctx, [&] {
         check_bb(params, cost);
         LGS_REQUIRE(scan->n >= 1, "empty scan");
-        LGS_REQUIRE(!sq || (long long)grid->w * grid->h < (1LL << 30), "square-error cost: map of 2^30 cells or more");
+        LGS_REQUIRE(!alt || (long long)grid->w * grid->h < (1LL << 30), "square-error or exact cost: map of 2^30 cells or more");
         auto pyr = pyramids(ctx, &grid, 1, params->node_height_max);   // ComputeCoarserMaps (:157-165)
         const double* const* pp = pyr[0].data();
         lgs_scan* s = const_cast<lgs_scan*>(scan);
-        run_bb(ctx, params, cost, &grid, &pp, &s, &initial, 1, DBL_MIN, out, false, sq);
+        run_bb(ctx, params, cost, &grid, &pp, &s, &initial, 1, DBL_MIN, out, false, alt);
     });
 }
 
@@ -1057,7 +1060,7 @@ extern "C" int lgs_bb_optimize_pose_query(lgs_ctx* ctx, const lgs_grid* grid, co
                                           const lgs_cost_ge_params* cost, const lgs_scan* scan,
                                           lgs_pose2d initial, lgs_rtcsm_summary* out)
 {
-    return bb_query_run(ctx, grid, params, cost, nullptr, scan, initial, out);
+    return bb_query_run(ctx, grid, params, cost, CostAlt{}, scan, initial, out);
 }
 
 extern "C" int lgs_bb_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_bb_params* params,
@@ -1066,16 +1069,16 @@ extern "C" int lgs_bb_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* gri
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq) return lgs_bb_optimize_pose_query(ctx, grid, params, sel.ge, scan, initial, out);
+    if (!sel.alt) return lgs_bb_optimize_pose_query(ctx, grid, params, sel.ge, scan, initial, out);
     if (!out) return LGS_ERR_INVALID_ARG;
     lgs_rtcsm_summary tmp;
-    const int rc = bb_query_run(ctx, grid, params, sel.ge, sel.sq, scan, initial, &tmp);
+    const int rc = bb_query_run(ctx, grid, params, sel.ge, sel.alt, scan, initial, &tmp);
     if (rc == LGS_OK) *out = tmp;
     return rc;
 }
 
 static int loop_detect_bb_run(lgs_ctx* ctx, const lgs_bb_params* params, const lgs_cost_ge_params* cost,
-                              const lgs_cost_sq_params* sq, double score_threshold, const lgs_loop_query* queries,
+                              CostAlt alt, double score_threshold, const lgs_loop_query* queries,
                               int num_queries, const lgs_loop_candidate* candidates, int num_candidates,
                               lgs_loop_result* results)
 {
@@ -1089,8 +1092,8 @@ static int loop_detect_bb_run(lgs_ctx* ctx, const lgs_bb_params* params, const l
         for (int q = 0; q < num_queries; ++q) {
             const lgs_loop_query& Q = queries[q];
             LGS_REQUIRE(Q.map, "loop query without a local map");
-            LGS_REQUIRE(!sq || (long long)Q.map->w * Q.map->h < (1LL << 30),
-                        "square-error cost: map of 2^30 cells or more");
+            LGS_REQUIRE(!alt || (long long)Q.map->w * Q.map->h < (1LL << 30),
+                        "square-error or exact cost: map of 2^30 cells or more");
             LGS_REQUIRE(Q.first_candidate == covered && Q.num_candidates >= 0 &&
                             Q.first_candidate + Q.num_candidates <= num_candidates,
                         "loop queries must cover the candidates contiguously and in order");
@@ -1126,7 +1129,7 @@ static int loop_detect_bb_run(lgs_ctx* ctx, const lgs_bb_params* params, const l
             std::vector<lgs_rtcsm_summary> sums(cand.size());
             if (!cand.empty())
                 run_bb(ctx, params, cost, grids.data(), pp.data(), sc.data(), poses.data(), (int)cand.size(),
-                       score_threshold, sums.data(), false, sq);
+                       score_threshold, sums.data(), false, alt);
             for (size_t k = 0; k < cand.size(); ++k) {
                 const lgs_loop_query& Q = queries[qof[k]];
                 lgs_loop_result& r = results[cand[k]];
@@ -1152,7 +1155,7 @@ extern "C" int lgs_loop_detect_bb(lgs_ctx* ctx, const lgs_bb_params* params, con
                                   const lgs_loop_candidate* candidates, int num_candidates,
                                   lgs_loop_result* results)
 {
-    return loop_detect_bb_run(ctx, params, cost, nullptr, score_threshold, queries, num_queries, candidates,
+    return loop_detect_bb_run(ctx, params, cost, CostAlt{}, score_threshold, queries, num_queries, candidates,
                               num_candidates, results);
 }
 
@@ -1164,14 +1167,14 @@ extern "C" int lgs_loop_detect_bb_cost(lgs_ctx* ctx, const lgs_bb_params* params
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq)
+    if (!sel.alt)
         return lgs_loop_detect_bb(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
                                   num_candidates, results);
     if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
     std::vector<lgs_loop_result> tmp;
     const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
     if (rc0 != LGS_OK) return rc0;
-    const int rc = loop_detect_bb_run(ctx, params, sel.ge, sel.sq, score_threshold, queries, num_queries, candidates,
+    const int rc = loop_detect_bb_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries, candidates,
                                       num_candidates, tmp.data());
     if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
     return rc;

@@ -333,7 +333,7 @@ size_t gs_item_bytes(const GSWindow& w, int Nvp)
 // every pose's score in (iy, ix, it) order; no summaries then (cost == null).
 void run_gs(lgs_ctx* ctx, const lgs_gs_params* p, const lgs_cost_ge_params* cost, const GSWindow& win,
             const lgs_grid* const* grids, lgs_scan* const* scans, const lgs_pose2d* init, int n, double nthr,
-            lgs_rtcsm_summary* out, double* dense_host = nullptr, const lgs_cost_sq_params* sq = nullptr)
+            lgs_rtcsm_summary* out, double* dense_host = nullptr, CostAlt alt = {})
 {
     const int nx = (int)win.dx.size(), ny = (int)win.dy.size(), nt = (int)win.dt.size();
     const long long poses = win.poses();
@@ -501,9 +501,13 @@ void run_gs(lgs_ctx* ctx, const lgs_gs_params* p, const lgs_cost_ge_params* cost
         o.fine_blocks = 0;
         best[(size_t)j] = bp;
     }
-    if (sq) {
-        // CostSquareError (:99-110): one launch over every item, whatever its map
-        cost_summaries_sq(ctx, grids, sq, scans, best.data(), n, out);
+    if (alt) {
+        // CostSquareError or the exact greedy-endpoint cost (:99-110): one launch over every
+        // item, whatever its map
+        if (alt.sq)
+            cost_summaries_sq(ctx, grids, alt.sq, scans, best.data(), n, out);
+        else
+            cost_summaries_gx(ctx, grids, cost, scans, best.data(), n, out);
         return;
     }
     // cost and covariance at the best poses (:99-110), grouped by map
@@ -542,9 +546,9 @@ extern "C" int lgs_gs_steps(double range, double step, double* out, int cap)
     }
 }
 
-// sq non-null: the cost step is CostSquareError's (k_sq_cost_batch)
+// alt: the cost step is CostSquareError's (k_sq_cost_batch) or the exact greedy-endpoint one (k_ge_cost_batch)
 static int gs_batch_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
-                        const lgs_cost_ge_params* cost, const lgs_cost_sq_params* sq, const lgs_scan* const* scans,
+                        const lgs_cost_ge_params* cost, CostAlt alt, const lgs_scan* const* scans,
                         const lgs_pose2d* initial, int n, double nthr, lgs_rtcsm_summary* out)
 {
     if (!ctx || !grid || !params || !cost || n < 0 || (n > 0 && (!scans || !initial || !out)))
@@ -559,7 +563,7 @@ static int gs_batch_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params*
             LGS_REQUIRE(scans[j] && scans[j]->n >= 1, "empty scan");
             sc[(size_t)j] = const_cast<lgs_scan*>(scans[j]);
         }
-        run_gs(ctx, params, cost, win, grids.data(), sc.data(), initial, n, nthr, out, nullptr, sq);
+        run_gs(ctx, params, cost, win, grids.data(), sc.data(), initial, n, nthr, out, nullptr, alt);
     });
 }
 
@@ -567,7 +571,7 @@ extern "C" int lgs_gs_optimize_pose_batch(lgs_ctx* ctx, const lgs_grid* grid, co
                                           const lgs_cost_ge_params* cost, const lgs_scan* const* scans,
                                           const lgs_pose2d* initial, int n, double nthr, lgs_rtcsm_summary* out)
 {
-    return gs_batch_run(ctx, grid, params, cost, nullptr, scans, initial, n, nthr, out);
+    return gs_batch_run(ctx, grid, params, cost, CostAlt{}, scans, initial, n, nthr, out);
 }
 
 // With the square-error cost a failing call leaves `out` as it found it.
@@ -577,12 +581,12 @@ extern "C" int lgs_gs_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* gri
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq) return lgs_gs_optimize_pose_batch(ctx, grid, params, sel.ge, scans, initial, n, nthr, out);
+    if (!sel.alt) return lgs_gs_optimize_pose_batch(ctx, grid, params, sel.ge, scans, initial, n, nthr, out);
     if (n < 0 || (n > 0 && !out)) return LGS_ERR_INVALID_ARG;
     std::vector<lgs_rtcsm_summary> tmp;
     const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)n); });
     if (rc0 != LGS_OK) return rc0;
-    const int rc = gs_batch_run(ctx, grid, params, sel.ge, sel.sq, scans, initial, n, nthr, tmp.data());
+    const int rc = gs_batch_run(ctx, grid, params, sel.ge, sel.alt, scans, initial, n, nthr, tmp.data());
     if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(lgs_rtcsm_summary) * (size_t)n);
     return rc;
 }
@@ -619,7 +623,7 @@ extern "C" int lgs_gs_dense_scores(lgs_ctx* ctx, const lgs_grid* grid, const lgs
 }
 
 static int loop_detect_gs_run(lgs_ctx* ctx, const lgs_gs_params* params, const lgs_cost_ge_params* cost,
-                              const lgs_cost_sq_params* sq, double score_threshold, const lgs_loop_query* queries,
+                              CostAlt alt, double score_threshold, const lgs_loop_query* queries,
                               int num_queries, const lgs_loop_candidate* candidates, int num_candidates,
                               lgs_loop_result* results)
 {
@@ -655,7 +659,7 @@ static int loop_detect_gs_run(lgs_ctx* ctx, const lgs_gs_params* params, const l
         if (num_candidates == 0) return;
         std::vector<lgs_rtcsm_summary> sums((size_t)num_candidates);
         run_gs(ctx, params, cost, win, grids.data(), sc.data(), poses.data(), num_candidates, score_threshold,
-               sums.data(), nullptr, sq);
+               sums.data(), nullptr, alt);
         for (int k = 0; k < num_candidates; ++k) {
             const lgs_loop_query& Q = queries[qof[(size_t)k]];
             const lgs_rtcsm_summary& s = sums[(size_t)k];
@@ -679,7 +683,7 @@ extern "C" int lgs_loop_detect_gs(lgs_ctx* ctx, const lgs_gs_params* params, con
                                   const lgs_loop_candidate* candidates, int num_candidates,
                                   lgs_loop_result* results)
 {
-    return loop_detect_gs_run(ctx, params, cost, nullptr, score_threshold, queries, num_queries, candidates,
+    return loop_detect_gs_run(ctx, params, cost, CostAlt{}, score_threshold, queries, num_queries, candidates,
                               num_candidates, results);
 }
 
@@ -691,14 +695,14 @@ extern "C" int lgs_loop_detect_gs_cost(lgs_ctx* ctx, const lgs_gs_params* params
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq)
+    if (!sel.alt)
         return lgs_loop_detect_gs(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
                                   num_candidates, results);
     if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
     std::vector<lgs_loop_result> tmp;
     const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
     if (rc0 != LGS_OK) return rc0;
-    const int rc = loop_detect_gs_run(ctx, params, sel.ge, sel.sq, score_threshold, queries, num_queries, candidates,
+    const int rc = loop_detect_gs_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries, candidates,
                                       num_candidates, tmp.data());
     if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
     return rc;

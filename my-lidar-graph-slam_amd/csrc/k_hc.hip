@@ -20,12 +20,19 @@
 //                 central-difference costs of the covariance follow in the
 //                 same launch
 //   k_hc_cost     the cost code on its own at a list of poses
+//   k_ge_cost_batch  one workgroup per (map, scan, sensor pose): the cost there
+//                 and at the six poses of ComputeGradient around it -- what the
+//                 branch-and-bound and grid-search matchers and their loop
+//                 detectors derive from the cost after their search
+//                 (LGS_COST_GREEDY_ENDPOINT_EXACT)
+//
+// The per-beam term and the chain live in ge_cost_device.hpp, which the
+// correlative pipeline's exact cost stage (k_rtcsm.hip k_cost_gx) shares.
 //
 // Workgroups never wait for one another and the walk is bounded by the pass
 // cap max(1, max_iterations).  The covariance, the normalized cost and the
 // summary's pose algebra are formed on the host with glibc.
-#include "lgs_internal.hpp"
-#include "glibc_math.hpp"
+#include "ge_cost_device.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -37,7 +44,6 @@ namespace {
 
 constexpr int kHCThreads = 1024;
 constexpr int kHCPoses = 6;                  // poses per cost pass (the six neighbours)
-constexpr int kHCMaxKernel = 16;             // documented cap of kernel_size
 constexpr int kHCMaxIter = 65536;            // documented cap of max_iterations
 constexpr size_t kHCLdsMax = 144 * 1024;     // term rows in LDS up to here (6 N doubles), else global rows
 constexpr size_t kHCRowsCap = size_t(1) << 30;   // global term rows of the matches of one launch
@@ -50,129 +56,6 @@ struct HCRecord {
     double lin_step, ang_step;
     int num_iterations, num_refinements, passes, cost_evals;
 };
-
-// One match of a launch (device memory).
-struct HCItem {
-    double sx, sy, st;          // sensor pose (Compound(initialPose, relPose))
-    double min_x, min_y, res;   // map geometry
-    double min_range, max_range;
-    int W, H, N, pad;
-    const double* map;
-    const double* ranges;
-    const double* angles;
-    double* rows;               // [6][N] term rows when they do not fit LDS
-    int* trace_move;            // [pass cap] or null
-    double* trace_cost;
-};
-
-// What every match of a launch shares.
-struct HCShared {
-    double lin_step, ang_step;
-    double hit_and_missed_dist, occupancy_threshold, scaling_factor;
-    const double* sq;           // lgs_hc_term_table, device copy
-    const double* term;
-    int max_iterations, max_refinements, K, trace_cap;
-    unsigned lds_bytes;         // dynamic LDS of the launch
-};
-
-// GridMap::Value(idx, unknown) on the dense view: outside the map unknown (0)
-__device__ __forceinline__ double hc_gval(const double* __restrict__ g, int W, int H, int x, int y)
-{
-    const bool inb = ((unsigned)x < (unsigned)W) & ((unsigned)y < (unsigned)H);
-    const size_t off = inb ? (size_t)y * W + x : 0;
-    const double v = gload(g + off);
-    return inb ? v : 0.0;
-}
-
-// WorldCoordinateToGridCellIndex (H/grid_map/grid_map.hpp:779-790) of one
-// coordinate.  Quotients beyond +-2^30 (no map has that many cells per axis)
-// are held there so that cell + k cannot wrap.
-__device__ __forceinline__ int hc_cell(double v, double mn, double res)
-{
-    const double f = floor((v - mn) / res);
-    return (int)fmin(fmax(f, -1073741824.0), 1073741824.0);
-}
-
-// The term of beam i at sensor pose (px, py, pt): exp(-0.5 * minSquaredDist /
-// variance) as the table holds it (:50-101), +0.0 for a filtered beam
-template <int KS>
-__device__ __forceinline__ double hc_term(const HCItem& it, const HCShared& sh, int i, double px, double py, double pt,
-                                          int* __restrict__ err)
-{
-    const double r = gload(it.ranges + i);
-    if (r >= it.max_range || r <= it.min_range) return 0.0;   // :52-53
-    // HitAndMissedPoint (H/sensor/sensor_data.hpp:177-198): one glibc sincos
-    const double th = pt + gload(it.angles + i);
-    if (!glm::gl_sincos_ok(th)) *err = 1;
-    double sn, cs;
-    glm::gl_sincos(th, &sn, &cs);
-    const double hx = px + r * cs;
-    const double hy = py + r * sn;
-    const double rm = r - sh.hit_and_missed_dist;
-    const double mx = px + rm * cs;
-    const double my = py + rm * sn;
-    const int hix = hc_cell(hx, it.min_x, it.res), hiy = hc_cell(hy, it.min_y, it.res);
-    const int mix = hc_cell(mx, it.min_x, it.res), miy = hc_cell(my, it.min_y, it.res);
-    const double* __restrict__ map = it.map;
-    const double* __restrict__ tsq = sh.sq;
-    const double* __restrict__ tterm = sh.term;
-    const int K = KS > 0 ? KS : sh.K;
-    const int D = 2 * K + 1;
-    double minSq = tsq[D * D];        // SquaredDistance(0, 0, K + 1, K + 1) (:66-67)
-    double term = tterm[D * D];
-    if constexpr (KS > 0) {
-        // every cell value loaded before any test: the loads are independent
-        constexpr int DD = (2 * KS + 1) * (2 * KS + 1);
-        double hv[DD], mv[DD];
-#pragma unroll
-        for (int q = 0; q < DD; ++q) {
-            hv[q] = hc_gval(map, it.W, it.H, hix + q % (2 * KS + 1) - KS, hiy + q / (2 * KS + 1) - KS);
-            mv[q] = hc_gval(map, it.W, it.H, mix + q % (2 * KS + 1) - KS, miy + q / (2 * KS + 1) - KS);
-        }
-#pragma unroll
-        for (int q = 0; q < DD; ++q) {   // ky outer, kx inner
-            if (hv[q] == 0.0 || mv[q] == 0.0) continue;                                          // :82-84
-            if (hv[q] < sh.occupancy_threshold || mv[q] > sh.occupancy_threshold) continue;      // :89-92
-            const double sq = tsq[q];
-            if (!(minSq < sq)) {   // std::min(sq, minSq) (:94-96)
-                minSq = sq;
-                term = tterm[q];
-            }
-        }
-    } else {
-        int q = 0;
-        for (int ky = -K; ky <= K; ++ky)
-            for (int kx = -K; kx <= K; ++kx, ++q) {
-                const double hv = hc_gval(map, it.W, it.H, hix + kx, hiy + ky);
-                const double mv = hc_gval(map, it.W, it.H, mix + kx, miy + ky);
-                if (hv == 0.0 || mv == 0.0) continue;
-                if (hv < sh.occupancy_threshold || mv > sh.occupancy_threshold) continue;
-                const double sq = tsq[q];
-                if (!(minSq < sq)) {
-                    minSq = sq;
-                    term = tterm[q];
-                }
-            }
-    }
-    return term;
-}
-
-// costValue = 0; costValue -= term, beams in order; costValue *= scale (:45, :101-104)
-__device__ __forceinline__ double hc_chain(const double* __restrict__ row, int N, double scale)
-{
-    double c = 0.0;
-    int i = 0;
-    for (; i + 8 <= N; i += 8) {
-        double t[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = row[i + j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) c -= t[j];
-    }
-    for (; i < N; ++i) c -= row[i];
-    c *= scale;
-    return c;
-}
 
 // Diagnostics build (make probe): thread 0 of block 0 adds up the 100 MHz wall
 // clock of the two phases of hc_costs and prints the sums after the walk.
@@ -228,6 +111,19 @@ __device__ __forceinline__ void hc_neighbours(double (*s_pose)[3], const double*
         s_pose[i][1] = best[1] + moveY[i] * lin;
         s_pose[i][2] = best[2] + moveTheta[i] * ang;
     }
+}
+
+// the poses of ComputeGradient around (x, y, th) (:119-136)
+__device__ __forceinline__ void hc_gradient_poses(double (*s_pose)[3], double x, double y, double th, double dl)
+{
+    const double da = 1e-2;
+    const double v[6][3] = { { x + dl, y + 0.0, th + 0.0 }, { x - dl, y - 0.0, th - 0.0 },
+                             { x + 0.0, y + dl, th + 0.0 }, { x - 0.0, y - dl, th - 0.0 },
+                             { x + 0.0, y + 0.0, th + da }, { x - 0.0, y - 0.0, th - da } };
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s_pose[i][j] = v[i][j];
 }
 
 template <int KS>
@@ -303,16 +199,7 @@ __global__ __launch_bounds__(kHCThreads) void k_hc(const HCItem* __restrict__ it
         if (!s_go) break;
     }
     // the poses of ComputeGradient (:119-136)
-    if (t0) {
-        const double x = s_best[0], y = s_best[1], th = s_best[2], dl = it.res, da = 1e-2;
-        const double v[6][3] = { { x + dl, y + 0.0, th + 0.0 }, { x - dl, y - 0.0, th - 0.0 },
-                                 { x + 0.0, y + dl, th + 0.0 }, { x - 0.0, y - dl, th - 0.0 },
-                                 { x + 0.0, y + 0.0, th + da }, { x - 0.0, y - 0.0, th - da } };
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) s_pose[i][j] = v[i][j];
-    }
+    if (t0) hc_gradient_poses(s_pose, s_best[0], s_best[1], s_best[2], it.res);
     __syncthreads();
     hc_costs<KS>(it, sh, s_pose, 6, s_cost, l_rows, in_lds, err);
     if (t0) {
@@ -357,6 +244,40 @@ __global__ __launch_bounds__(kHCThreads) void k_hc_cost(const HCItem* __restrict
     if ((int)threadIdx.x < np) out[k0 + threadIdx.x] = s_cost[threadIdx.x];
 }
 
+// Item blockIdx.x: Cost at its sensor pose into out[7 b] and, with want_grad,
+// at the six poses of ComputeGradient into out[7 b + 1 .. 7 b + 6].  The items
+// of a launch may differ in map and resolution: each names its own term table.
+template <int KS>
+__global__ __launch_bounds__(kHCThreads) void k_ge_cost_batch(const HCItem* __restrict__ items, HCShared sh,
+                                                              int want_grad, double* __restrict__ out,
+                                                              int* __restrict__ err)
+{
+    extern __shared__ double l_rows[];
+    __shared__ double s_pose[kHCPoses][3];
+    __shared__ double s_cost[kHCPoses];
+    const HCItem& it = items[blockIdx.x];
+    sh.sq = it.tab;
+    sh.term = it.tab + hc_table_len(KS > 0 ? KS : sh.K);
+    const bool in_lds = sizeof(double) * (size_t)kHCPoses * (size_t)it.N <= (size_t)sh.lds_bytes;
+    const bool t0 = threadIdx.x == 0;
+    if (t0) {
+        s_pose[0][0] = it.sx;
+        s_pose[0][1] = it.sy;
+        s_pose[0][2] = it.st;
+    }
+    __syncthreads();
+    hc_costs<KS>(it, sh, s_pose, 1, s_cost, l_rows, in_lds, err);
+    double* __restrict__ o = out + 7 * (size_t)blockIdx.x;
+    if (t0) {
+        o[0] = s_cost[0];
+        hc_gradient_poses(s_pose, it.sx, it.sy, it.st, it.res);
+    }
+    if (!want_grad) return;
+    __syncthreads();
+    hc_costs<KS>(it, sh, s_pose, 6, s_cost, l_rows, in_lds, err);
+    if ((int)threadIdx.x < 6) o[1 + threadIdx.x] = s_cost[threadIdx.x];
+}
+
 // ------------------------------------------------------------------ host
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -364,24 +285,6 @@ bool hc_cost_ok(const lgs_cost_ge_params* c, double res)
 {
     return c && c->kernel_size >= 0 && c->kernel_size <= kHCMaxKernel && std::isfinite(res) && res > 0.0 &&
            std::isfinite(c->standard_deviation) && c->standard_deviation > 0.0;
-}
-
-// GridMap::SquaredDistance (H/grid_map/grid_map.hpp:894-902) of every kernel
-// offset, then of (K + 1, K + 1); exp(-0.5 * sq / variance) with libm's exp (:101)
-void hc_table(const lgs_cost_ge_params* c, double res, std::vector<double>& sq, std::vector<double>& term)
-{
-    const int K = c->kernel_size;
-    const double variance = c->standard_deviation * c->standard_deviation;
-    sq.clear();
-    for (int ky = -K; ky <= K; ++ky)
-        for (int kx = -K; kx <= K; ++kx) {
-            const double dX = kx * res, dY = ky * res;
-            sq.push_back(dX * dX + dY * dY);
-        }
-    const double d = (K + 1) * res;
-    sq.push_back(d * d + d * d);
-    term.resize(sq.size());
-    for (size_t q = 0; q < sq.size(); ++q) term[q] = std::exp(-0.5 * sq[q] / variance);
 }
 
 void check_hc(const lgs_hc_params* p)
@@ -706,5 +609,191 @@ extern "C" int lgs_cost_ge_exact(lgs_ctx* ctx, const lgs_grid* grid, const lgs_c
         if (*(const int*)(pin + ob) != 0)
             throw Error(LGS_ERR_INTERNAL, "exact cost: an angle lies outside the restated sincos domain");
         std::memcpy(out, pin, sizeof(double) * (size_t)n);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// The cost and its covariance at many (map, scan, sensor pose) items
+// (LGS_COST_GREEDY_ENDPOINT_EXACT for the branch-and-bound and grid-search
+// matchers)
+// ---------------------------------------------------------------------------
+
+// The device term table of (cost, res): lgs_hc_term_table's squared distances,
+// then its terms.  Built and uploaded (on the context's stream, ahead of the
+// launches that read it) the first time a key is seen.
+const double* lgs_ctx::ge_table(const lgs_cost_ge_params* cost, double res)
+{
+    for (const GeTable& t : ge_tables)
+        if (t.K == cost->kernel_size && t.sd == cost->standard_deviation && t.res == res) return t.dev;
+    if (ge_tables.size() >= 64) {   // a caller sweeping parameters: start over
+        sync();
+        if (hi) LGS_HIP_CHECK(hipStreamSynchronize(hi));   // a chunk's tail may still read a table there
+        for (GeTable& t : ge_tables) (void)hipFree(t.dev);
+        ge_tables.clear();
+    }
+    GeTable t;
+    t.K = cost->kernel_size;
+    t.sd = cost->standard_deviation;
+    t.res = res;
+    t.dev = nullptr;
+    std::vector<double> sq, term;
+    hc_table(cost, res, sq, term);
+    t.host = sq;
+    t.host.insert(t.host.end(), term.begin(), term.end());
+    LGS_HIP_CHECK(hipSetDevice(device));
+    LGS_HIP_CHECK(hipMalloc((void**)&t.dev, sizeof(double) * t.host.size()));
+    ge_tables.push_back(std::move(t));
+    const GeTable& k = ge_tables.back();   // the vector's buffer moves with it: k.host.data() stays
+    LGS_HIP_CHECK(hipMemcpyAsync(k.dev, k.host.data(), sizeof(double) * k.host.size(), hipMemcpyHostToDevice, stream));
+    return k.dev;
+}
+
+namespace {
+
+// ComputeGradient (:138-141) and ComputeCovariance (:147-171) from the costs at
+// the six central-difference poses
+void ge_covariance(const double* c7, double res, double* cov)
+{
+    const double dl = res, da = 1e-2;
+    const double g[3] = { 0.5 * (c7[1] - c7[2]) / dl, 0.5 * (c7[3] - c7[4]) / dl, 0.5 * (c7[5] - c7[6]) / da };
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) cov[3 * a + b] = g[a] * g[b];
+    cov[0] += 0.01;
+    cov[4] += 0.01;
+    cov[8] += 0.01;
+}
+
+// costs7[7 j ..]: Cost at sensor[j] and (want_grad) at the six gradient poses.
+// Chunks are runs of at most kHCChunk items in order, all launched before the
+// one synchronisation; they run one after another and share the global rows.
+void run_ge_batch(lgs_ctx* ctx, const lgs_cost_ge_params* cost, const lgs_grid* const* grids,
+                  const lgs_scan* const* scans, const lgs_pose2d* sensor, int n, bool want_grad, double* costs7)
+{
+    for (int j = 0; j < n; ++j) {
+        LGS_REQUIRE(grids[j] && grids[j]->d && scans[j] && scans[j]->n >= 1, "exact cost: null map or empty scan");
+        LGS_REQUIRE(hc_cost_ok(cost, grids[j]->res), "exact cost: kernel size in [0, 16], resolution and standard "
+                                                     "deviation finite and > 0");
+        LGS_REQUIRE((long long)grids[j]->w * grids[j]->h < (1LL << 30), "exact cost: map of 2^30 cells or more");
+        LGS_REQUIRE(pose_finite(sensor[j]), "exact cost: pose not finite");
+    }
+    if (n == 0) return;
+    for (int k = 0; k < n; ++k) grid_acquire(ctx, grids[k]);
+    LGS_HIP_CHECK(hipSetDevice(ctx->device));
+    struct Chunk { int j0, j1; size_t lds, rows; };
+    std::vector<Chunk> chunks;
+    size_t rows_max = 0;
+    for (int j = 0; j < n;) {
+        Chunk c{ j, j, 0, 0 };
+        for (; c.j1 < n && c.j1 - c.j0 < kHCChunk; ++c.j1) {
+            const size_t rb = hc_rows_bytes(scans[c.j1]->n);
+            if (rb > kHCLdsMax) {
+                if (c.j1 > c.j0 && c.rows + align256(rb) > kHCRowsCap) break;
+                c.rows += align256(rb);
+            } else
+                c.lds = std::max(c.lds, rb);
+        }
+        rows_max = std::max(rows_max, c.rows);
+        chunks.push_back(c);
+        j = c.j1;
+    }
+    scans_to_device(ctx, scans, n);
+    char* rows = rows_max ? (char*)ctx->ensure(S_HC0, rows_max) : nullptr;
+    const size_t ob = align256(sizeof(double) * 7 * (size_t)n);
+    char* small = (char*)ctx->ensure(S_HC1, ob + 256);
+    double* d_out = (double*)small;
+    int* d_err = (int*)(small + ob);
+    LGS_HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
+    if (!want_grad) LGS_HIP_CHECK(hipMemsetAsync(d_out, 0, ob, ctx->stream));
+    std::vector<HCItem> items((size_t)n);
+    for (const Chunk& c : chunks) {
+        size_t roff = 0;
+        for (int j = c.j0; j < c.j1; ++j) {
+            HCItem& it = items[(size_t)j];
+            it = hc_item(grids[j], cost, scans[j], sensor[j]);
+            it.tab = ctx->ge_table(cost, grids[j]->res);
+            const size_t b = hc_rows_bytes(scans[j]->n);
+            if (b > kHCLdsMax) {
+                it.rows = (double*)(rows + roff);
+                roff += align256(b);
+            }
+        }
+    }
+    Upload up(ctx);
+    const size_t io = up.append(items.data(), items.size());
+    up.flush();
+    HCShared sh = hc_shared(nullptr, cost);
+    for (const Chunk& c : chunks) {
+        sh.lds_bytes = (unsigned)c.lds;
+        const HCItem* d_items = up.at<HCItem>(io) + c.j0;
+        if (cost->kernel_size == 1) {
+            hc_allow_lds(k_ge_cost_batch<1>, c.lds);
+            hipLaunchKernelGGL(k_ge_cost_batch<1>, dim3(c.j1 - c.j0), dim3(kHCThreads), c.lds, ctx->stream, d_items, sh,
+                               want_grad ? 1 : 0, d_out + 7 * (size_t)c.j0, d_err);
+        } else {
+            hc_allow_lds(k_ge_cost_batch<0>, c.lds);
+            hipLaunchKernelGGL(k_ge_cost_batch<0>, dim3(c.j1 - c.j0), dim3(kHCThreads), c.lds, ctx->stream, d_items, sh,
+                               want_grad ? 1 : 0, d_out + 7 * (size_t)c.j0, d_err);
+        }
+        LGS_HIP_CHECK(hipGetLastError());
+    }
+    char* pin = (char*)ctx->ensure_pinned(ob + 256);
+    LGS_HIP_CHECK(hipMemcpyAsync(pin, small, ob + 256, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    if (*(const int*)(pin + ob) != 0)
+        throw Error(LGS_ERR_INTERNAL, "exact cost: an angle lies outside the restated sincos domain");
+    std::memcpy(costs7, pin, sizeof(double) * 7 * (size_t)n);
+}
+
+}  // namespace
+
+namespace lgs {
+// What the branch-and-bound and grid-search matchers derive from their cost
+// function after the search (scan_matcher_branch_bound.cpp:146-153,
+// scan_matcher_grid_search.cpp:97-107), the greedy-endpoint cost bit for bit:
+// normalized cost, estimated pose and covariance at best[j]
+void cost_summaries_gx(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_ge_params* cost,
+                       lgs_scan* const* scans, const lgs_pose2d* best, int n, lgs_rtcsm_summary* out)
+{
+    if (n <= 0) return;
+    std::vector<double> c7(7 * (size_t)n);
+    run_ge_batch(ctx, cost, grids, scans, best, n, true, c7.data());
+    for (int j = 0; j < n; ++j) {
+        out[j].normalized_cost = c7[7 * (size_t)j] / (double)scans[j]->n;
+        out[j].estimated_pose = move_backward(best[j], scans[j]->rel);
+        ge_covariance(&c7[7 * (size_t)j], grids[j]->res, out[j].covariance);
+    }
+}
+}  // namespace lgs
+
+extern "C" int lgs_cost_ge_exact_batch(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_ge_params* cost,
+                                       const lgs_scan* const* scans, const lgs_pose2d* sensor_poses, int n,
+                                       double* out_cost, double* out_covariance)
+{
+    if (!ctx || !cost || n < 0 || (n > 0 && (!grids || !scans || !sensor_poses || !out_cost)))
+        return LGS_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        std::vector<double> c7(7 * (size_t)n);
+        run_ge_batch(ctx, cost, grids, scans, sensor_poses, n, out_covariance != nullptr, c7.data());
+        for (int j = 0; j < n; ++j) {
+            out_cost[j] = c7[7 * (size_t)j];
+            if (out_covariance) ge_covariance(&c7[7 * (size_t)j], grids[j]->res, out_covariance + 9 * (size_t)j);
+        }
+    });
+}
+
+extern "C" int lgs_summaries_apply_cost_ge_exact(lgs_ctx* ctx, const lgs_grid* const* grids,
+                                                 const lgs_cost_ge_params* cost, const lgs_scan* const* scans,
+                                                 lgs_rtcsm_summary* summaries, int n)
+{
+    if (!ctx || !cost || n < 0 || (n > 0 && (!grids || !scans || !summaries))) return LGS_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        std::vector<double> c7(7 * (size_t)n);
+        std::vector<lgs_pose2d> poses((size_t)n);
+        for (int j = 0; j < n; ++j) poses[(size_t)j] = summaries[j].best_sensor_pose;
+        run_ge_batch(ctx, cost, grids, scans, poses.data(), n, true, c7.data());
+        for (int j = 0; j < n; ++j) {
+            summaries[j].normalized_cost = c7[7 * (size_t)j] / (double)scans[j]->n;
+            ge_covariance(&c7[7 * (size_t)j], grids[j]->res, summaries[j].covariance);
+        }
     });
 }

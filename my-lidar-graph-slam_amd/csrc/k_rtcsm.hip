@@ -30,9 +30,13 @@
 //   k_cost_sq   in their place for a matcher built with CostSquareError: Cost
 //               and ComputeGradient's sums at the best pose
 //               (C/mapping/cost_function_square_error.cpp:21-109).
+//   k_cost_gx   in k_cost's place for LGS_COST_GREEDY_ENDPOINT_EXACT: the same
+//               seven costs bit for bit (ge_cost_device.hpp: restated sincos,
+//               table terms, beam-order sums; no guards, no host fix-up).
 #include "lgs_internal.hpp"
 #include "fast_cell.hpp"
 #include "sq_cost_stage.hpp"
+#include "ge_cost_device.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -108,6 +112,7 @@ struct MatchItem {
     double* poses7;
     int4* cidx;
     double* terms;
+    const double* ge_tab;    // k_cost_gx: the term table of the item's cost and resolution (lgs_ctx::ge_table)
     // lean projection (LGS_OPT_LEAN_PROJECT): k_project
     // does not run; k_beams writes these two tables and every kernel that
     // stages a superblock-base, coarse-base or cell row forms it itself
@@ -3745,6 +3750,69 @@ __global__ __launch_bounds__(kSqThreads) void k_cost_sq(Items items, unsigned ld
 }
 
 // --------------------------------------------------------------------------
+// exact greedy-endpoint cost, the stage that takes k_cost's
+// place for LGS_COST_GREEDY_ENDPOINT_EXACT: one workgroup per (pose, item), as
+// k_cost, at the seven poses the search left in poses7 (k_replay,
+// k_match_small), with the hill-climbing cost's own code (ge_cost_device.hpp:
+// restated gl_sincos, IEEE cells, the window ky outer / kx inner, the term
+// selected from the host's libm table).  The terms go to dynamic LDS (cost_lds)
+// or, beyond kCostLdsTerms beams, to the item's global term rows; one lane
+// then performs costValue -= term in beam order and costValue *= scale.  The
+// cells are exact, so there are no guard records and nothing for the host to
+// fix up.  gx_err[pose] reports an angle outside the restated sincos domain.
+// --------------------------------------------------------------------------
+template <int KS>
+__global__ __launch_bounds__(kCostThreads) void k_cost_gx(Items items, DevTs dts)
+{
+    const DtsScope dts_scope(dts);
+    const MatchItem& mi = items[blockIdx.y];
+    const CostPlan& cp = mi.cp;
+    extern __shared__ double lterms[];   // [min(max N of the launch, kCostLdsTerms)] (cost_lds)
+    __shared__ int s_err;
+    const int pi = blockIdx.x;
+    const int N = cp.N;
+    const bool in_lds = N <= kCostLdsTerms;
+    double* __restrict__ g_row = mi.terms + (size_t)pi * N;
+    HCItem it{};
+    it.min_x = cp.min_x;
+    it.min_y = cp.min_y;
+    it.res = cp.res;
+    it.min_range = cp.min_range;
+    it.max_range = cp.max_range;
+    it.W = cp.W;
+    it.H = cp.H;
+    it.N = N;
+    it.map = mi.grid;
+    it.ranges = mi.ranges;
+    it.angles = mi.angles;
+    HCShared sh{};
+    sh.hit_and_missed_dist = cp.hit_and_missed_dist;
+    sh.occupancy_threshold = cp.occupancy_threshold;
+    sh.scaling_factor = cp.scaling_factor;
+    sh.K = cp.kernel_size;
+    sh.sq = mi.ge_tab;
+    sh.term = mi.ge_tab + hc_table_len(KS > 0 ? KS : cp.kernel_size);
+    const double px = gload(mi.poses7 + 3 * pi), py = gload(mi.poses7 + 3 * pi + 1),
+                 pt = gload(mi.poses7 + 3 * pi + 2);
+    if (threadIdx.x == 0) s_err = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < N; i += kCostThreads) {
+        const double t = hc_term<KS>(it, sh, i, px, py, pt, &s_err);
+        if (in_lds)
+            lterms[i] = t;
+        else
+            g_row[i] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        RtcsmRecord* rec = mi.rec;
+        rec->costs[pi] = in_lds ? hc_chain(lterms, N, sh.scaling_factor) : hc_chain(g_row, N, sh.scaling_factor);
+        rec->gx_err[pi] = s_err;
+    }
+}
+#define KCOSTGX(ks) ((ks) == 1 ? k_cost_gx<1> : k_cost_gx<0>)
+
+// --------------------------------------------------------------------------
 // Small windows: the whole search of a window whose coarse
 // lattice holds ONE block per angle (2 winX < lr and 2 winY < lr: the launcher
 // JSON frontend window, +-0.1 m at 5 cm with LowRes 5) in one launch, one
@@ -4330,6 +4398,7 @@ struct BatchShape {
     int frows = 1;
     int kernel_size = 0;
     bool sq = false;        // the cost stage is k_cost_sq (a matcher built with CostSquareError)
+    bool gx = false;        // the cost stage is k_cost_gx (LGS_COST_GREEDY_ENDPOINT_EXACT)
     WorkList wl{};          // kept-superblock work list (wl.cnt null: k_coarse_rows)
 };
 
@@ -4767,7 +4836,8 @@ struct ScanOptions {
 
 // The cost stage of a batch's n items at the poses the search left in poses7:
 // the greedy-endpoint cost at the 7 poses (k_cost), or, for a matcher built
-// with CostSquareError (B.sq), k_cost_sq alone.
+// with CostSquareError (B.sq), k_cost_sq alone; or, for the exact
+// greedy-endpoint cost (B.gx), k_cost_gx at the 7 poses.
 void enqueue_cost(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::vector<MatchItem>& items, int n,
                   int inject)
 {
@@ -4787,6 +4857,15 @@ void enqueue_cost(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::v
         return;
     }
     const double kk = (2.0 * B.kernel_size + 1) * (2.0 * B.kernel_size + 1);
+    if (B.gx) {
+        const int tok_ = ctx->timing_begin(K_COST_GX, 8.0 * 7.0 * 2.0 * kk * nbeams);
+        if (!ctx->skipped(K_COST_GX))
+            hipLaunchKernelGGL(KCOSTGX(B.kernel_size), dim3(7, n), dim3(kCostThreads), cost_lds(items), st, d_items,
+                               ctx->dts(tok_));
+        ctx->timing_end(tok_);
+        LGS_HIP_CHECK(hipGetLastError());
+        return;
+    }
     const int tok_ = ctx->timing_begin(K_COST, 8.0 * 7.0 * 2.0 * kk * nbeams);
     if (!ctx->skipped(K_COST))
         hipLaunchKernelGGL(KCOST(B.kernel_size), dim3(7, n), dim3(kCostThreads), cost_lds(items), st, d_items,
@@ -5296,6 +5375,7 @@ void check_coarse(const lgs_grid* grid, const lgs_grid* coarse)
 }
 
 const char* const kSqDomainError = "square-error cost: an angle lies outside the restated sincos domain";
+const char* const kGxDomainError = "exact greedy-endpoint cost: an angle lies outside the restated sincos domain";
 
 // Run n matches as one batch: the items share the search parameters and the
 // map geometry; sets are the distinct coarse maps (set_of[j] = item j's).
@@ -5319,6 +5399,7 @@ struct InFlight {
     unsigned* flag = nullptr;     // its completion flag in the pinned record buffer
     unsigned post_gen = 0;
     bool sq_err = false;          // k_cost_sq met an angle outside the restated sincos domain
+    bool gx_err = false;          // k_cost_gx did
 };
 
 // Lean projection (LGS_OPT_LEAN_PROJECT): only when every kernel enqueue_items
@@ -5343,8 +5424,9 @@ bool lean_rows(const lgs_ctx* ctx, const BatchShape& B, const std::vector<MatchI
 void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge_params* cost,
                     const lgs_grid* const* grids, lgs_scan* const* scans, const lgs_pose2d* init, int n,
                     double nthr, std::vector<PlaneSet>& sets, const int* set_of, lgs_rtcsm_summary* out,
-                    InFlight& F, const lgs_cost_sq_params* sq = nullptr)
+                    InFlight& F, CostAlt alt = {})
 {
+    const lgs_cost_sq_params* sq = alt.sq;
     LGS_HIP_CHECK(hipSetDevice(ctx->device));
     LGS_REQUIRE(n >= 1 && n <= kMaxBatchItems, "batch of 1..64 matches (run_chunked splits larger ones)");
     std::vector<MatchItem> items((size_t)n);
@@ -5368,6 +5450,7 @@ void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost
             it.cp.min_range = std::max(sq->usable_range_min, scans[j]->min_range);
             it.cp.max_range = std::min(sq->usable_range_max, scans[j]->max_range);
         }
+        if (alt.gx) it.ge_tab = ctx->ge_table(cost, grids[j]->res);   // uploaded here, ahead of the split to the tail's stream
         B.Tmax = std::max(B.Tmax, it.pl.T);
         B.NvMax = std::max(B.NvMax, nv);
         Nmax = std::max(Nmax, scans[j]->n);
@@ -5397,6 +5480,7 @@ void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost
                         grids[j]->h <= 8192;
     B.kernel_size = cost->kernel_size;
     B.sq = sq != nullptr;
+    B.gx = alt.gx;
     B.nsegMax = (int)(((long long)B.Tmax * B.P + kSelSeg - 1) / kSelSeg);
     // one coarse block per angle: the whole search in one launch, straight
     // from the fine map (no caller-supplied coarse map to honour)
@@ -5622,7 +5706,7 @@ void finish_matches(lgs_ctx* ctx, InFlight& F)
                 rerun = true;
                 slow = 1;
             }
-            if (!rerun && !opt.cost_patches && !B.sq) {
+            if (!rerun && !opt.cost_patches && !B.sq && !B.gx) {
                 const CostPlan& cp = items[j].cp;
                 if (check_cost_guards(ctx, items[j].pl, cp, scans[j], rec, cpatch, full_cost)) {
                     if (full_cost) {
@@ -5671,6 +5755,8 @@ void finish_matches(lgs_ctx* ctx, InFlight& F)
         }
         finish_summary(items[j].pl, scans[j], init[j], pruned, rec, &out[j], B.sq);
         if (B.sq && rec.sq_err) F.sq_err = true;
+        if (B.gx)
+            for (int k = 0; k < 7; ++k) F.gx_err = F.gx_err || rec.gx_err[k] != 0;
         out[j].guard_hits = guard_hits;
         out[j].fixups = fixups;
         out[j].slow_path = slow;
@@ -5686,13 +5772,14 @@ void finish_matches(lgs_ctx* ctx, InFlight& F)
 void run_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge_params* cost,
                  const lgs_grid* const* grids, lgs_scan* const* scans, const lgs_pose2d* init, int n,
                  double nthr, std::vector<PlaneSet>& sets, const int* set_of, lgs_rtcsm_summary* out,
-                 const lgs_cost_sq_params* sq = nullptr)
+                 CostAlt alt = {})
 {
     InFlight F;
     ctx->bank = 0;
-    launch_matches(ctx, params, cost, grids, scans, init, n, nthr, sets, set_of, out, F, sq);
+    launch_matches(ctx, params, cost, grids, scans, init, n, nthr, sets, set_of, out, F, alt);
     finish_matches(ctx, F);
     if (F.sq_err) throw Error(LGS_ERR_INTERNAL, kSqDomainError);
+    if (F.gx_err) throw Error(LGS_ERR_INTERNAL, kGxDomainError);
 }
 
 
@@ -5703,14 +5790,14 @@ constexpr int kSplitMin = 16;   // smallest chunk of a split call
 void run_chunked(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge_params* cost,
                  const lgs_grid* const* grids, lgs_scan* const* scans, const lgs_pose2d* init, int n,
                  double nthr, const std::vector<PlaneSet>& sets_all, const int* set_of, lgs_rtcsm_summary* out,
-                 const lgs_cost_sq_params* sq = nullptr)
+                 CostAlt alt = {})
 {
     // two chunks in flight: chunk c + 1 is launched (on the other bank)
     // before the host takes chunk c's results, so the device never waits for
     // the host between chunks of one call
     InFlight fl[2];
     bool busy[2] = { false, false };
-    bool sq_err = false;   // reported once every chunk of the call has finished
+    bool sq_err = false, gx_err = false;   // reported once every chunk of the call has finished
     int c = 0;
     // a call of 2 x kSplitMin .. kMaxBatch matches runs as two chunks, so that
     // the two banks overlap even then (an 8-rank shard of the 512-candidate
@@ -5733,12 +5820,13 @@ void run_chunked(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge
             ctx->bank = b;
             fl[b] = InFlight{};
             launch_matches(ctx, params, cost, grids + j0, scans + j0, init + j0, m, nthr, sets, so.data(), out + j0,
-                           fl[b], sq);
+                           fl[b], alt);
             busy[b] = true;
             if (busy[b ^ 1]) {
                 finish_matches(ctx, fl[b ^ 1]);
                 busy[b ^ 1] = false;
                 sq_err = sq_err || fl[b ^ 1].sq_err;
+                gx_err = gx_err || fl[b ^ 1].gx_err;
             }
         }
         const int last = (c - 1) & 1;
@@ -5746,6 +5834,7 @@ void run_chunked(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge
             finish_matches(ctx, fl[last]);
             busy[last] = false;
             sq_err = sq_err || fl[last].sq_err;
+            gx_err = gx_err || fl[last].gx_err;
         }
     } catch (...) {
         ctx->bank = 0;
@@ -5753,6 +5842,7 @@ void run_chunked(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge
     }
     ctx->bank = 0;
     if (sq_err) throw Error(LGS_ERR_INTERNAL, kSqDomainError);
+    if (gx_err) throw Error(LGS_ERR_INTERNAL, kGxDomainError);
 }
 
 }  // namespace
@@ -5956,14 +6046,19 @@ extern "C" int lgs_rtcsm_optimize_pose_query_batch(lgs_ctx* ctx, const lgs_grid*
 }
 
 // ---- the same four with either cost function (lgs_cost_spec).  Kind 0 is the
-// entry point above; kind 1 runs the same search with k_cost_sq as its cost
-// stage, into a buffer of its own so that a failing call writes nothing.
+// entry point above; kinds 1 and 2 run the same search with k_cost_sq or
+// k_cost_gx as its cost stage, into a buffer of its own so that a failing call
+// writes nothing.
 namespace {
-void check_sq_maps(const lgs_grid* const* grids, int n)
+// the maps' caps of the square-error cost and of the exact greedy-endpoint cost
+void check_alt_maps(const CostAlt& alt, const lgs_grid* const* grids, int n)
 {
-    for (int j = 0; j < n; ++j)
+    for (int j = 0; j < n; ++j) {
         LGS_REQUIRE(grids[j] && (long long)grids[j]->w * grids[j]->h < (1LL << 30),
-                    "square-error cost: null map or map of 2^30 cells or more");
+                    "square-error or exact cost: null map or map of 2^30 cells or more");
+        LGS_REQUIRE(!alt.gx || (std::isfinite(grids[j]->res) && grids[j]->res > 0.0),
+                    "exact cost: map resolution finite and > 0");
+    }
 }
 template <class F>
 int with_own_summaries(lgs_ctx* ctx, lgs_rtcsm_summary* out, int n, F&& f)
@@ -5985,17 +6080,17 @@ extern "C" int lgs_rtcsm_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* 
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq) return lgs_rtcsm_optimize_pose_batch(ctx, grid, coarse, params, sel.ge, scans, initial, n, nthr, out);
+    if (!sel.alt) return lgs_rtcsm_optimize_pose_batch(ctx, grid, coarse, params, sel.ge, scans, initial, n, nthr, out);
     if (!ctx || !out || !scans || !initial || n < 0 || !grid || !coarse) return LGS_ERR_INVALID_ARG;
     if (n == 0) return LGS_OK;
     return with_own_summaries(ctx, out, n, [&](lgs_rtcsm_summary* o) {
-        check_sq_maps(&grid, 1);
+        check_alt_maps(sel.alt, &grid, 1);
         std::vector<PlaneSet> sets(1);
         sets[0].coarse = coarse;
         const std::vector<int> set_of((size_t)n, 0);
         const std::vector<const lgs_grid*> grids((size_t)n, grid);
         run_chunked(ctx, params, sel.ge, grids.data(), const_cast<lgs_scan* const*>(scans), initial, n, nthr, sets,
-                    set_of.data(), o, sel.sq);
+                    set_of.data(), o, sel.alt);
     });
 }
 
@@ -6006,15 +6101,15 @@ extern "C" int lgs_rtcsm_optimize_pose_cost(lgs_ctx* ctx, const lgs_grid* grid, 
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq) return lgs_rtcsm_optimize_pose(ctx, grid, coarse, params, sel.ge, scan, initial, nthr, out);
+    if (!sel.alt) return lgs_rtcsm_optimize_pose(ctx, grid, coarse, params, sel.ge, scan, initial, nthr, out);
     if (!ctx || !out || !grid || !coarse || !scan) return LGS_ERR_INVALID_ARG;
     return with_own_summaries(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
-        check_sq_maps(&grid, 1);
+        check_alt_maps(sel.alt, &grid, 1);
         std::vector<PlaneSet> sets(1);
         sets[0].coarse = coarse;
         const int set0 = 0;
         lgs_scan* s = const_cast<lgs_scan*>(scan);
-        run_matches(ctx, params, sel.ge, &grid, &s, &initial, 1, nthr, sets, &set0, o, sel.sq);
+        run_matches(ctx, params, sel.ge, &grid, &s, &initial, 1, nthr, sets, &set0, o, sel.alt);
     });
 }
 
@@ -6024,15 +6119,15 @@ extern "C" int lgs_rtcsm_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* 
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq) return lgs_rtcsm_optimize_pose_query(ctx, grid, params, sel.ge, scan, initial, out);
+    if (!sel.alt) return lgs_rtcsm_optimize_pose_query(ctx, grid, params, sel.ge, scan, initial, out);
     if (!ctx || !grid || !params || !out || !scan) return LGS_ERR_INVALID_ARG;
     return with_own_summaries(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
-        check_sq_maps(&grid, 1);
+        check_alt_maps(sel.alt, &grid, 1);
         std::vector<PlaneSet> sets(1);
         sets[0].fine = grid;
         const int set0 = 0;
         lgs_scan* s = const_cast<lgs_scan*>(scan);
-        run_matches(ctx, params, sel.ge, &grid, &s, &initial, 1, DBL_MIN, sets, &set0, o, sel.sq);
+        run_matches(ctx, params, sel.ge, &grid, &s, &initial, 1, DBL_MIN, sets, &set0, o, sel.alt);
     });
 }
 
@@ -6043,7 +6138,7 @@ extern "C" int lgs_rtcsm_optimize_pose_query_batch_cost(lgs_ctx* ctx, const lgs_
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq) return lgs_rtcsm_optimize_pose_query_batch(ctx, grids, params, sel.ge, scans, initial, n, out);
+    if (!sel.alt) return lgs_rtcsm_optimize_pose_query_batch(ctx, grids, params, sel.ge, scans, initial, n, out);
     if (!ctx || !grids || !params || !scans || !initial || !out || n < 0) return LGS_ERR_INVALID_ARG;
     if (n == 0) return LGS_OK;
     return with_own_summaries(ctx, out, n, [&](lgs_rtcsm_summary* o) {
@@ -6054,9 +6149,9 @@ extern "C" int lgs_rtcsm_optimize_pose_query_batch_cost(lgs_ctx* ctx, const lgs_
             sets[j].fine = grids[j];
             set_of[j] = j;
         }
-        check_sq_maps(grids, n);
+        check_alt_maps(sel.alt, grids, n);
         run_chunked(ctx, params, sel.ge, grids, const_cast<lgs_scan* const*>(scans), initial, n, DBL_MIN, sets,
-                    set_of.data(), o, sel.sq);
+                    set_of.data(), o, sel.alt);
     });
 }
 
@@ -6200,7 +6295,7 @@ extern "C" int lgs_cost_greedy_endpoint(lgs_ctx* ctx, const lgs_grid* grid,
 // Candidates are independent, so the queries whose local maps share a size
 // are matched together in batches (each query's coarse map built once per batch).
 static int loop_detect_rtcsm_run(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost_ge_params* cost,
-                                 const lgs_cost_sq_params* sq, double score_threshold,
+                                 CostAlt alt, double score_threshold,
                                  const lgs_loop_query* queries, int num_queries,
                                  const lgs_loop_candidate* candidates, int num_candidates,
                                  lgs_loop_result* results)
@@ -6215,8 +6310,7 @@ static int loop_detect_rtcsm_run(lgs_ctx* ctx, const lgs_rtcsm_params* params, c
         for (int q = 0; q < num_queries; ++q) {
             const lgs_loop_query& Q = queries[q];
             LGS_REQUIRE(Q.map, "loop query without a local map");
-            LGS_REQUIRE(!sq || (long long)Q.map->w * Q.map->h < (1LL << 30),
-                        "square-error cost: map of 2^30 cells or more");
+            if (alt) check_alt_maps(alt, &Q.map, 1);
             LGS_REQUIRE(Q.first_candidate == covered && Q.num_candidates >= 0 &&
                             Q.first_candidate + Q.num_candidates <= num_candidates,
                         "loop queries must cover the candidates contiguously and in order");
@@ -6256,7 +6350,7 @@ static int loop_detect_rtcsm_run(lgs_ctx* ctx, const lgs_rtcsm_params* params, c
             if (cand.empty()) continue;
             std::vector<lgs_rtcsm_summary> sums(cand.size());
             run_chunked(ctx, params, cost, grids.data(), scans.data(), poses.data(), (int)cand.size(),
-                        score_threshold, sets, set_of.data(), sums.data(), sq);
+                        score_threshold, sets, set_of.data(), sums.data(), alt);
             for (size_t k = 0; k < cand.size(); ++k) {
                 const int ci = cand[k];
                 int qi = 0;
@@ -6287,7 +6381,7 @@ extern "C" int lgs_loop_detect_rtcsm(lgs_ctx* ctx, const lgs_rtcsm_params* param
                                      const lgs_loop_candidate* candidates, int num_candidates,
                                      lgs_loop_result* results)
 {
-    return loop_detect_rtcsm_run(ctx, params, cost, nullptr, score_threshold, queries, num_queries, candidates,
+    return loop_detect_rtcsm_run(ctx, params, cost, CostAlt{}, score_threshold, queries, num_queries, candidates,
                                  num_candidates, results);
 }
 
@@ -6299,14 +6393,14 @@ extern "C" int lgs_loop_detect_rtcsm_cost(lgs_ctx* ctx, const lgs_rtcsm_params* 
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq)
+    if (!sel.alt)
         return lgs_loop_detect_rtcsm(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
                                      num_candidates, results);
     if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
     std::vector<lgs_loop_result> tmp;
     const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
     if (rc0 != LGS_OK) return rc0;
-    const int rc = loop_detect_rtcsm_run(ctx, params, sel.ge, sel.sq, score_threshold, queries, num_queries,
+    const int rc = loop_detect_rtcsm_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries,
                                          candidates, num_candidates, tmp.data());
     if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
     return rc;
@@ -6447,9 +6541,9 @@ struct LoopShard {
 
 }  // namespace
 
-// every shard's detector gets the same cost function (sq null: greedy endpoint)
+// every shard's detector gets the same cost function (alt empty: greedy endpoint, k_cost)
 static int loop_detect_rtcsm_multi_run(lgs_ctx* const* ctxs, int num_ctx, const lgs_rtcsm_params* params,
-                                       const lgs_cost_ge_params* cost, const lgs_cost_sq_params* sq,
+                                       const lgs_cost_ge_params* cost, CostAlt alt,
                                        double score_threshold, const lgs_loop_query* queries, int num_queries,
                                        const lgs_loop_candidate* candidates, int num_candidates,
                                        lgs_loop_result* results)
@@ -6459,7 +6553,7 @@ static int loop_detect_rtcsm_multi_run(lgs_ctx* const* ctxs, int num_ctx, const 
         if (!ctxs[k]) return LGS_ERR_INVALID_ARG;
     lgs_ctx* const c0 = ctxs[0];
     if (num_ctx == 1 || num_candidates <= 1)
-        return loop_detect_rtcsm_run(c0, params, cost, sq, score_threshold, queries, num_queries, candidates,
+        return loop_detect_rtcsm_run(c0, params, cost, alt, score_threshold, queries, num_queries, candidates,
                                      num_candidates, results);
     if (!params || !cost || (num_queries > 0 && !queries) || num_queries < 0 || num_candidates < 0 ||
         (num_candidates > 0 && (!candidates || !results)))
@@ -6491,7 +6585,7 @@ static int loop_detect_rtcsm_multi_run(lgs_ctx* const* ctxs, int num_ctx, const 
             try {
                 if (hipSetDevice(sh.ctx->device) != hipSuccess) throw Error(LGS_ERR_HIP, "hipSetDevice failed");
                 sh.prepare(queries, num_queries, candidates);
-                sh.status = loop_detect_rtcsm_run(sh.ctx, params, cost, sq, score_threshold, sh.qs.data(),
+                sh.status = loop_detect_rtcsm_run(sh.ctx, params, cost, alt, score_threshold, sh.qs.data(),
                                                   (int)sh.qs.size(), sh.cs.data(), (int)sh.cs.size(),
                                                   results + sh.lo);
                 if (sh.status != LGS_OK) sh.error = sh.ctx->last_error;
@@ -6523,7 +6617,7 @@ extern "C" int lgs_loop_detect_rtcsm_multi(lgs_ctx* const* ctxs, int num_ctx, co
                                            const lgs_loop_candidate* candidates, int num_candidates,
                                            lgs_loop_result* results)
 {
-    return loop_detect_rtcsm_multi_run(ctxs, num_ctx, params, cost, nullptr, score_threshold, queries, num_queries,
+    return loop_detect_rtcsm_multi_run(ctxs, num_ctx, params, cost, CostAlt{}, score_threshold, queries, num_queries,
                                        candidates, num_candidates, results);
 }
 
@@ -6535,7 +6629,7 @@ extern "C" int lgs_loop_detect_rtcsm_multi_cost(lgs_ctx* const* ctxs, int num_ct
 {
     CostSel sel;
     if (const int rc = cost_select(cost, &sel)) return rc;
-    if (!sel.sq)
+    if (!sel.alt)
         return lgs_loop_detect_rtcsm_multi(ctxs, num_ctx, params, sel.ge, score_threshold, queries, num_queries,
                                            candidates, num_candidates, results);
     if (!ctxs || num_ctx < 1 || !ctxs[0] || num_candidates < 0 || (num_candidates > 0 && !results))
@@ -6543,7 +6637,7 @@ extern "C" int lgs_loop_detect_rtcsm_multi_cost(lgs_ctx* const* ctxs, int num_ct
     std::vector<lgs_loop_result> tmp;
     const int rc0 = guarded(ctxs[0], [&] { tmp.resize((size_t)num_candidates); });
     if (rc0 != LGS_OK) return rc0;
-    const int rc = loop_detect_rtcsm_multi_run(ctxs, num_ctx, params, sel.ge, sel.sq, score_threshold, queries,
+    const int rc = loop_detect_rtcsm_multi_run(ctxs, num_ctx, params, sel.ge, sel.alt, score_threshold, queries,
                                                num_queries, candidates, num_candidates, tmp.data());
     if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
     return rc;

@@ -194,7 +194,8 @@ const char* const kKernelNames[K_NUM_KERNELS] = { "k_project", "k_coarse", "k_se
                                                   "k_fine", "k_replay", "k_cost", "k_precompute",
                                                   "k_linsolve", "k_ray_emit", "k_ray_apply",
                                                   "k_super", "k_super_planes", "k_bb_score", "k_bb_expand",
-                                                  "k_coarse_aux", "k_match_small", "k_gs_score", "k_cost_sq" };
+                                                  "k_coarse_aux", "k_match_small", "k_gs_score", "k_cost_sq",
+                                                  "k_cost_gx" };
 }
 
 int lgs_ctx::next_stamp()
@@ -353,6 +354,9 @@ void lgs_ctx::release()
     aux_bytes.clear();
     if (zero) hipFree(zero);
     zero = nullptr;
+    for (auto& t : ge_tables)
+        if (t.dev) hipFree(t.dev);
+    ge_tables.clear();
     for (int b = 0; b < 2; ++b) {
         if (dts_buf[b]) hipFree(dts_buf[b]);
         dts_buf[b] = nullptr;

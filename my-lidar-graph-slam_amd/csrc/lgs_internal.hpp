@@ -120,6 +120,7 @@ struct RtcsmRecord {
     double L;             // lower bound used for pruning
     double costs[7];
     unsigned long long coarse_evals;   // blocks k_coarse evaluated (superblock pruning)
+    int gx_err[8];        // k_cost_gx, per pose: a beam angle left the restated sincos domain ([7]: unused)
     GuardRec guard[kGuardInline];
     CostGuardRec cost_guard[kGuardInline];
 };
@@ -254,6 +255,7 @@ enum KernelId { K_PROJECT = 0, K_COARSE, K_SEED, K_SELECT, K_FINE, K_REPLAY, K_C
                 K_MATCH_SMALL,  // k_match_small: a small window's whole search (one coarse block per angle)
                 K_GS_SCORE,     // k_gs_score: the grid-search matcher's score + workgroup argmax pass
                 K_COST_SQ,      // k_cost_sq: the correlative pipeline's square-error cost stage
+                K_COST_GX,      // k_cost_gx: the correlative pipeline's exact greedy-endpoint cost stage
                 K_NUM_KERNELS };
 extern const char* const kKernelNames[K_NUM_KERNELS];
 struct PendingTiming {
@@ -494,6 +496,18 @@ struct lgs_ctx {
     // hipStreamSynchronize (LGS_OPT_SPIN_SYNC 0)
     bool spin_sync = true;
     void sync();
+
+    // Device term tables of the exact greedy-endpoint cost (k_hc.hip ge_table:
+    // lgs_hc_term_table's squared distances, then its terms), keyed by (kernel
+    // size, standard deviation, resolution) and uploaded on `stream` when new
+    struct GeTable {
+        int K;
+        double sd, res;
+        std::vector<double> host;   // kept while the upload may be in flight
+        double* dev;
+    };
+    std::vector<GeTable> ge_tables;
+    const double* ge_table(const lgs_cost_ge_params* cost, double res);
 
     void* ensure(int slot, size_t bytes);
     // grow-only auxiliary device buffers indexed by number (per-level
@@ -864,14 +878,29 @@ int guarded(lgs_ctx* ctx, F&& f)
     }
 }
 
-// The cost function of a `_cost` entry point: sq is null for the greedy-endpoint
-// cost (ge = &spec->ge), else ge is an all-zero stand-in that no kernel reads.
+// The cost step of a search when it is not the greedy-endpoint stage with its
+// tree sum and guards (k_cost): CostSquareError (sq), or the greedy-endpoint
+// cost bit for bit (gx, LGS_COST_GREEDY_ENDPOINT_EXACT).  Neither: k_cost.
+struct CostAlt {
+    const lgs_cost_sq_params* sq = nullptr;
+    bool gx = false;
+    explicit operator bool() const { return sq || gx; }
+};
+// The cost function of a `_cost` entry point: for the square-error cost ge is
+// an all-zero stand-in that no kernel reads, else ge = &spec->ge.
 struct CostSel {
     const lgs_cost_ge_params* ge = nullptr;
-    const lgs_cost_sq_params* sq = nullptr;
+    CostAlt alt;
 };
-// LGS_OK, or LGS_ERR_INVALID_ARG for a null spec, an unknown kind or
-// non-finite square-error ranges (checked before any device work)
+// the caps of the exact greedy-endpoint cost that do not depend on the map
+inline bool ge_exact_cost_ok(const lgs_cost_ge_params* c)
+{
+    return c && c->kernel_size >= 0 && c->kernel_size <= 16 && std::isfinite(c->standard_deviation) &&
+           c->standard_deviation > 0.0;
+}
+// LGS_OK, or LGS_ERR_INVALID_ARG for a null spec, an unknown kind,
+// non-finite square-error ranges or an exact greedy-endpoint cost beyond its
+// caps (checked before any device work)
 inline int cost_select(const lgs_cost_spec* spec, CostSel* sel)
 {
     static const lgs_cost_ge_params no_ge = {};
@@ -880,15 +909,24 @@ inline int cost_select(const lgs_cost_spec* spec, CostSel* sel)
         sel->ge = &spec->ge;
         return LGS_OK;
     }
+    if (spec->kind == LGS_COST_GREEDY_ENDPOINT_EXACT) {
+        if (!ge_exact_cost_ok(&spec->ge)) return LGS_ERR_INVALID_ARG;
+        sel->ge = &spec->ge;
+        sel->alt.gx = true;
+        return LGS_OK;
+    }
     if (spec->kind != LGS_COST_SQUARE_ERROR) return LGS_ERR_INVALID_ARG;
     if (!std::isfinite(spec->sq.usable_range_min) || !std::isfinite(spec->sq.usable_range_max))
         return LGS_ERR_INVALID_ARG;
     sel->ge = &no_ge;
-    sel->sq = &spec->sq;
+    sel->alt.sq = &spec->sq;
     return LGS_OK;
 }
 // k_hc_sq.hip: the square-error cost step of the bb and gs matchers
 void cost_summaries_sq(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_sq_params* cost,
+                       lgs_scan* const* scans, const lgs_pose2d* best, int n, lgs_rtcsm_summary* out);
+// k_hc.hip: the exact greedy-endpoint cost step of the bb and gs matchers
+void cost_summaries_gx(lgs_ctx* ctx, const lgs_grid* const* grids, const lgs_cost_ge_params* cost,
                        lgs_scan* const* scans, const lgs_pose2d* best, int n, lgs_rtcsm_summary* out);
 
 // f(i) for i in [0, n) on a persistent pool of host threads (at most 16

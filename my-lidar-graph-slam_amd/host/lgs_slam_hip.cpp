@@ -175,15 +175,17 @@ static lgs_cost_spec sq_spec(const lgs_cost_sq_params* cost)
     return spec;
 }
 
-// the cost function a loop detector's matcher was constructed with: the
-// reference's detector calls its matcher's OptimizePose, so that cost function
-// produces mEstimatedCovMat (C/mapping/loop_detector_real_time_correlative.cpp:96-125)
+// the cost function a search matcher was constructed with; a loop detector
+// uses its matcher's: the reference's detector calls its matcher's
+// OptimizePose, so that cost function produces mEstimatedCovMat
+// (C/mapping/loop_detector_real_time_correlative.cpp:96-125).  A greedy-endpoint
+// cost built with mExact selects the bit-exact kind.
 template <class Matcher>
 static lgs_cost_spec spec_of(const Matcher& m)
 {
     if (m.CostSquareError()) return sq_spec(m.CostSquareError());
     lgs_cost_spec spec{};
-    spec.kind = LGS_COST_GREEDY_ENDPOINT;
+    spec.kind = m.Exact() ? LGS_COST_GREEDY_ENDPOINT_EXACT : LGS_COST_GREEDY_ENDPOINT;
     spec.ge = m.Cost();
     return spec;
 }
@@ -200,6 +202,7 @@ ScanMatcherRealTimeCorrelativeHip::ScanMatcherRealTimeCorrelativeHip(DevicePtr d
     // values surface as LGS_ERR_INVALID_ARG from the first OptimizePose
     mParams = { lowResolution, rangeX, rangeY, rangeTheta, scanRangeMax };
     mCost = ge_of(c);
+    mExact = c.mExact;
 }
 
 ScanMatcherRealTimeCorrelativeHip::ScanMatcherRealTimeCorrelativeHip(DevicePtr dev, const CostSquareErrorParams& c,
@@ -215,8 +218,8 @@ ScanMatcherRealTimeCorrelativeHip::ScanMatcherRealTimeCorrelativeHip(DevicePtr d
 
 ScanMatchingSummary ScanMatcherRealTimeCorrelativeHip::OptimizePose(const ScanMatchingQuery& q)
 {
-    if (CostSquareError()) {
-        const lgs_cost_spec spec = sq_spec(CostSquareError());
+    if (CostSquareError() || mExact) {
+        const lgs_cost_spec spec = spec_of(*this);
         mDev->Check(lgs_rtcsm_optimize_pose_query_cost(mDev->Handle(), q.mGridMap->Handle(), &mParams, &spec,
                                                        q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                     "lgs_rtcsm_optimize_pose_query_cost");
@@ -234,8 +237,8 @@ ScanMatchingSummary ScanMatcherRealTimeCorrelativeHip::OptimizePose(const Device
                                                                     const RobotPose2D<double>& initialPose,
                                                                     double thr) const
 {
-    if (CostSquareError()) {
-        const lgs_cost_spec spec = sq_spec(CostSquareError());
+    if (CostSquareError() || mExact) {
+        const lgs_cost_spec spec = spec_of(*this);
         mDev->Check(lgs_rtcsm_optimize_pose_cost(mDev->Handle(), gridMap.Handle(), precompMap.Handle(), &mParams,
                                                  &spec, scanData->Handle(), to_c(initialPose), thr, &mLast),
                     "lgs_rtcsm_optimize_pose_cost");
@@ -265,6 +268,7 @@ ScanMatcherBranchBoundHip::ScanMatcherBranchBoundHip(DevicePtr dev, const ScoreP
 {
     mParams = { nodeHeightMax, rangeX, rangeY, rangeTheta, scanRangeMax, sf.mUsableRangeMin, sf.mUsableRangeMax };
     mCost = ge_of(c);
+    mExact = c.mExact;
 }
 
 ScanMatcherBranchBoundHip::ScanMatcherBranchBoundHip(DevicePtr dev, const ScorePixelAccurateParams& sf,
@@ -280,8 +284,8 @@ ScanMatcherBranchBoundHip::ScanMatcherBranchBoundHip(DevicePtr dev, const ScoreP
 
 ScanMatchingSummary ScanMatcherBranchBoundHip::OptimizePose(const ScanMatchingQuery& q)
 {
-    if (CostSquareError()) {
-        const lgs_cost_spec spec = sq_spec(CostSquareError());
+    if (CostSquareError() || mExact) {
+        const lgs_cost_spec spec = spec_of(*this);
         mDev->Check(lgs_bb_optimize_pose_query_cost(mDev->Handle(), q.mGridMap->Handle(), &mParams, &spec,
                                                     q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                     "lgs_bb_optimize_pose_query_cost");
@@ -304,8 +308,8 @@ ScanMatchingSummary ScanMatcherBranchBoundHip::OptimizePose(const DeviceGrid& gr
         throw Error(LGS_ERR_INVALID_ARG, "ScanMatcherBranchBoundHip: one precomputed map per node height needed");
     const lgs_scan* s = scanData->Handle();
     const lgs_pose2d p = to_c(initialPose);
-    if (CostSquareError()) {
-        const lgs_cost_spec spec = sq_spec(CostSquareError());
+    if (CostSquareError() || mExact) {
+        const lgs_cost_spec spec = spec_of(*this);
         mDev->Check(lgs_bb_optimize_pose_batch_cost(mDev->Handle(), gridMap.Handle(), pyr.data(), &mParams, &spec, &s,
                                                     &p, 1, thr, &mLast),
                     "lgs_bb_optimize_pose_batch_cost");
@@ -341,6 +345,7 @@ ScanMatcherGridSearchHip::ScanMatcherGridSearchHip(DevicePtr dev, const ScorePix
     // values surface as LGS_ERR_INVALID_ARG from the first OptimizePose
     mParams = { rangeX, rangeY, rangeTheta, stepX, stepY, stepTheta, sf.mUsableRangeMin, sf.mUsableRangeMax };
     mCost = ge_of(c);
+    mExact = c.mExact;
 }
 
 ScanMatcherGridSearchHip::ScanMatcherGridSearchHip(DevicePtr dev, const ScorePixelAccurateParams& sf,
@@ -355,8 +360,8 @@ ScanMatcherGridSearchHip::ScanMatcherGridSearchHip(DevicePtr dev, const ScorePix
 
 ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const ScanMatchingQuery& q)
 {
-    if (CostSquareError()) {
-        const lgs_cost_spec spec = sq_spec(CostSquareError());
+    if (CostSquareError() || mExact) {
+        const lgs_cost_spec spec = spec_of(*this);
         mDev->Check(lgs_gs_optimize_pose_query_cost(mDev->Handle(), q.mGridMap->Handle(), &mParams, &spec,
                                                     q.mScanData->Handle(), to_c(q.mInitialPose), &mLast),
                     "lgs_gs_optimize_pose_query_cost");
@@ -373,8 +378,8 @@ ScanMatchingSummary ScanMatcherGridSearchHip::OptimizePose(const DeviceGrid& gri
 {
     const lgs_scan* s = scanData->Handle();
     const lgs_pose2d p = to_c(initialPose);
-    if (CostSquareError()) {
-        const lgs_cost_spec spec = sq_spec(CostSquareError());
+    if (CostSquareError() || mExact) {
+        const lgs_cost_spec spec = spec_of(*this);
         mDev->Check(lgs_gs_optimize_pose_batch_cost(mDev->Handle(), gridMap.Handle(), &mParams, &spec, &s, &p, 1, thr,
                                                     &mLast),
                     "lgs_gs_optimize_pose_batch_cost");

@@ -195,6 +195,13 @@ struct CostGreedyEndpointParams {
     double mHitAndMissedDist = 0.075, mOccupancyThreshold = 0.1;
     int mKernelSize = 1;
     double mScalingFactor = 0.05, mStandardDeviation = 1.0;
+    // The search matchers (correlative, branch-and-bound, grid search) and the
+    // loop detectors over them evaluate this cost after their search.  false:
+    // the pipeline's default stage, normalized cost and covariance within 1e-5
+    // of the reference's.  true: the reference's bytes (the `_cost` entry
+    // points with LGS_COST_GREEDY_ENDPOINT_EXACT; kernel
+    // size at most 16).  The hill-climbing matcher is exact either way.
+    bool mExact = false;
     static CostGreedyEndpointParams FromLauncherJson(double usableMin, double usableMax, double hitMissed,
                                                      double occThr, int kernelSize, double jsonStdDev,
                                                      double jsonScale);
@@ -238,10 +245,13 @@ public:
     const lgs_cost_ge_params& Cost() const { return mCost; }
     // the square-error cost of a matcher constructed with one, else null
     const lgs_cost_sq_params* CostSquareError() const { return mSquareError ? &mCostSq : nullptr; }
+    // constructed with CostGreedyEndpointParams::mExact
+    bool Exact() const { return mExact; }
     const DevicePtr& Dev() const { return mDev; }
 
 private:
     DevicePtr mDev;
+    bool mExact = false;
     lgs_rtcsm_params mParams{};
     lgs_cost_ge_params mCost{};
     lgs_cost_sq_params mCostSq{};
@@ -278,10 +288,13 @@ public:
     const lgs_cost_ge_params& Cost() const { return mCost; }
     // the square-error cost of a matcher constructed with one, else null
     const lgs_cost_sq_params* CostSquareError() const { return mSquareError ? &mCostSq : nullptr; }
+    // constructed with CostGreedyEndpointParams::mExact
+    bool Exact() const { return mExact; }
     const DevicePtr& Dev() const { return mDev; }
 
 private:
     DevicePtr mDev;
+    bool mExact = false;
     lgs_bb_params mParams{};
     lgs_cost_ge_params mCost{};
     lgs_cost_sq_params mCostSq{};
@@ -310,10 +323,13 @@ public:
     const lgs_cost_ge_params& Cost() const { return mCost; }
     // the square-error cost of a matcher constructed with one, else null
     const lgs_cost_sq_params* CostSquareError() const { return mSquareError ? &mCostSq : nullptr; }
+    // constructed with CostGreedyEndpointParams::mExact
+    bool Exact() const { return mExact; }
     const DevicePtr& Dev() const { return mDev; }
 
 private:
     DevicePtr mDev;
+    bool mExact = false;
     lgs_gs_params mParams{};
     lgs_cost_ge_params mCost{};
     lgs_cost_sq_params mCostSq{};

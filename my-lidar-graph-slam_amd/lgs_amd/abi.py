@@ -51,7 +51,7 @@ LGS_OPT_FAST_ROWS = 37       # lean batches: certified fast hit-point cells in t
 KERNEL_IDS = ["k_project", "k_coarse", "k_seed", "k_select", "k_fine", "k_replay", "k_cost", "k_precompute",
               "k_linsolve", "k_ray_emit", "k_ray_apply", "k_super", "k_super_planes", "k_bb_score",
               "k_bb_expand", "k_coarse_aux", "k_match_small", "k_gs_score",
-              "k_cost_sq"]   # lgs_ctx_kernel_stats order
+              "k_cost_sq", "k_cost_gx"]   # lgs_ctx_kernel_stats order
 
 
 class Pose2D(C.Structure):
@@ -154,6 +154,7 @@ class CostSQParams(C.Structure):
 
 LGS_COST_GREEDY_ENDPOINT = 0
 LGS_COST_SQUARE_ERROR = 1
+LGS_COST_GREEDY_ENDPOINT_EXACT = 2   # the greedy-endpoint cost of `ge`, bit for bit
 
 
 class CostSpec(C.Structure):
@@ -161,8 +162,13 @@ class CostSpec(C.Structure):
     _fields_ = [("kind", C.c_int), ("ge", CostGEParams), ("sq", CostSQParams)]
 
 
-def cost_spec(cost) -> "CostSpec":
-    """the CostSpec of a CostGEParams or a CostSQParams"""
+def cost_spec(cost, exact: bool = False) -> "CostSpec":
+    """the CostSpec of a CostGEParams or a CostSQParams; exact=True (greedy
+    endpoint only) selects the bit-exact kind LGS_COST_GREEDY_ENDPOINT_EXACT"""
+    if exact:
+        if not isinstance(cost, CostGEParams):
+            raise TypeError("exact=True takes a CostGEParams")
+        return CostSpec(LGS_COST_GREEDY_ENDPOINT_EXACT, cost, CostSQParams())
     if isinstance(cost, CostSpec):
         return cost
     if isinstance(cost, CostSQParams):
@@ -402,6 +408,11 @@ _PROTOS = [
                                               C.POINTER(C.c_double)]),
     ("lgs_summaries_apply_cost_sq", C.c_int, [_P, C.POINTER(_P), C.POINTER(CostSQParams), C.POINTER(_P),
                                               C.POINTER(RtcsmSummary), C.c_int]),
+    ("lgs_cost_ge_exact_batch", C.c_int, [_P, C.POINTER(_P), C.POINTER(CostGEParams), C.POINTER(_P),
+                                          C.POINTER(Pose2D), C.c_int, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)]),
+    ("lgs_summaries_apply_cost_ge_exact", C.c_int, [_P, C.POINTER(_P), C.POINTER(CostGEParams), C.POINTER(_P),
+                                                    C.POINTER(RtcsmSummary), C.c_int]),
     ("lgs_hc_sq_optimize_pose_query", C.c_int, [_P, _P, C.POINTER(HCParams), C.POINTER(CostSQParams), _P, Pose2D,
                                                 C.POINTER(HCSummary)]),
     ("lgs_hc_sq_optimize_pose_batch", C.c_int, [_P, C.POINTER(_P), C.POINTER(HCParams), C.POINTER(CostSQParams),
@@ -951,6 +962,43 @@ class Context:
             C.memmove(C.byref(arr, k * C.sizeof(RtcsmSummary)), C.byref(s), C.sizeof(RtcsmSummary))
         self.check(self.lib.lgs_summaries_apply_cost_sq(self.h, garr, C.byref(cost), sarr, arr, n),
                    "summaries_apply_cost_sq")
+        return list(arr)[:n]
+
+    # ---- the greedy-endpoint cost bit for bit, for the search matchers ----
+    def cost_ge_exact_batch(self, grids, cost: "CostGEParams", scans, sensor_poses, covariance: bool = False):
+        """CostGreedyEndpoint::Cost and, with covariance=True, ComputeCovariance
+        of item j at sensor_poses[j] on grids[j] with scans[j] (a single grid
+        or scan serves every item), the reference's bytes: costs [n], or
+        (costs, covariances [n, 9])"""
+        n = len(sensor_poses)
+        if not isinstance(grids, (list, tuple)):
+            grids = [grids] * n
+        if not isinstance(scans, (list, tuple)):
+            scans = [scans] * n
+        garr = (_P * max(1, n))(*[g.h for g in grids])
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in sensor_poses])
+        out = np.zeros(max(1, n))
+        cov = np.zeros((max(1, n), 9)) if covariance else None
+        self.check(self.lib.lgs_cost_ge_exact_batch(self.h, garr, C.byref(cost), sarr, poses, n, dptr(out),
+                                                    dptr(cov) if covariance else None),
+                   "cost_ge_exact_batch")
+        return (out[:n], cov[:n]) if covariance else out[:n]
+
+    def summaries_apply_cost_ge_exact(self, grids, cost: "CostGEParams", scans, summaries):
+        """the summaries of rtcsm / bb / gs matches as LGS_COST_GREEDY_ENDPOINT_EXACT
+        returns them: normalized cost and covariance at best_sensor_pose replaced
+        by the reference's bytes, every other field kept.  Returns new copies."""
+        n = len(summaries)
+        if not isinstance(grids, (list, tuple)):
+            grids = [grids] * n
+        garr = (_P * max(1, n))(*[g.h for g in grids])
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        arr = (RtcsmSummary * max(1, n))()
+        for k, s in enumerate(summaries):
+            C.memmove(C.byref(arr, k * C.sizeof(RtcsmSummary)), C.byref(s), C.sizeof(RtcsmSummary))
+        self.check(self.lib.lgs_summaries_apply_cost_ge_exact(self.h, garr, C.byref(cost), sarr, arr, n),
+                   "summaries_apply_cost_ge_exact")
         return list(arr)[:n]
 
     def hc_sq_optimize_pose_query(self, grid, params: "HCParams", cost: "CostSQParams", scan, init) -> "HCSummary":

@@ -77,9 +77,10 @@ def hip_detect_fn(ctx: "abi.Context", maps: Sequence[LocalMap], cands: Sequence[
                   params: "abi.RtcsmParams", cost, threshold: float
                   ) -> Callable[[List[Tuple[int, int, int]], int, int], np.ndarray]:
     """Per-rank matcher on the GPU: uploads the maps its block needs once.
-    cost: the detector's matcher's cost function, a CostGEParams or a CostSQParams
-    (the records' normalized_cost and covariance are then CostSquareError's); the
-    same holds for hip_detect_fn_bb and hip_detect_fn_gs."""
+    cost: the detector's matcher's cost function, a CostGEParams, a CostSQParams
+    (the records' normalized_cost and covariance are then CostSquareError's) or a
+    CostSpec such as abi.cost_spec(ge, exact=True) (the greedy-endpoint values
+    bit for bit); the same holds for hip_detect_fn_bb and hip_detect_fn_gs."""
     grids = {}
     scans = {}
 
