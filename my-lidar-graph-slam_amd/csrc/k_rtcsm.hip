@@ -170,9 +170,11 @@ struct PlaneJob {
 // 8-bit superblock units (r06, octet layouts): 4 fp16 round-up maxima (bits
 // 16 i of v, i < 4) -> 4 bytes ceil(255 h) (exact: h has 11 significant
 // bits, so 255 h is exact in fp32, and ceil(255 h) / 255 >= h).  The bound is
-// then an exact integer sum / 255 (no fp32 partials).  A value above 1 (not an
-// occupancy probability) sets *over: the set's bounds are disabled (negflag,
-// as for negative cells).  Bit patterns of +0 and positive fp16 values order
+// then an exact integer sum / 255 (no fp32 partials).  A value that is not
+// <= 1 (above 1, +inf, NaN: not an occupancy probability) sets *over: the
+// set's bounds are disabled (negflag, as for negative cells; a NaN cell is
+// flagged where its round-up is written, since that round-up is +0).  Bit
+// patterns of +0 and positive fp16 values order
 // like the values, so the maxima taken on them stay maxima here.
 __device__ __forceinline__ unsigned quad_u8(unsigned long long v, bool& over)
 {
@@ -180,7 +182,7 @@ __device__ __forceinline__ unsigned quad_u8(unsigned long long v, bool& over)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const float h = (float)__builtin_bit_cast(_Float16, (unsigned short)(v >> (16 * i)));
-        over |= h > 1.0f;
+        over |= !(h <= 1.0f);   // above 1, +inf or NaN
         const float q = fminf(fmaxf(ceilf(h * 255.0f), 0.0f), 255.0f);
         r |= (unsigned)q << (8 * i);
     }
@@ -197,7 +199,7 @@ __global__ __launch_bounds__(256) void k_planes16(const double* __restrict__ P, 
     if (i >= n) return;
     const double v = P[i];
     P16[i] = half_round_up_bits(v);
-    if (v < 0.0) *negflag = pgen;
+    if (!(v >= 0.0)) *negflag = pgen;   // negative or NaN (its round-up is +0: no bound)
 }
 
 // Generation-tagged counter (gen << 32 | count): a word left by an earlier
@@ -904,7 +906,7 @@ __global__ __launch_bounds__(256) void k_decimate_jobs(const DecimJob* __restric
     j.D[o] = v;
     if (j.D16) {
         j.D16[o] = half_round_up_bits(v);
-        if (v < 0.0) *j.negflag = j.pgen;
+        if (!(v >= 0.0)) *j.negflag = j.pgen;   // negative or NaN
     }
 }
 
@@ -1121,8 +1123,10 @@ __global__ __launch_bounds__(1024) void k_coarse(Items items, const double* __re
 // The bound needs nonnegative terms (occupancy probabilities are); a negative
 // cell stamps *negflag with this build's generation (the precompute or
 // k_planes16, which write the planes' fp16 round-ups) and k_super then keeps
-// every superblock.  NaN cells round to +0 and so are skipped by the max: a
-// block whose sum is NaN fails c > thr and is never selected anyway.
+// every superblock.  A NaN cell rounds to +0 (a max skips it), which bounds
+// nothing, and a value above 1 has no 8-bit unit: whatever is not 0 <= v <= 1
+// stamps the flag the same way (the writers of the fp16 round-ups test
+// !(v >= 0), the superblock passes test the round-ups against 1).
 // k_super_planes: one workgroup per (tile of kSPX padded columns x kSPY
 // padded rows, plane, set).  A tile spans a config-2 plane's whole width
 // (Wqp = 240; 224-column tiles left a second tile per row with 16 columns).
@@ -1248,14 +1252,22 @@ __global__ __launch_bounds__((SPX + 3 + 63) / 64 * 64) void k_super_planes(const
     // task (row, sub-phase, chunk), chunk fastest
     constexpr int kChunks = kQ / 8;
     typedef SuperT s8 __attribute__((ext_vector_type(8)));
+    typedef unsigned short b8 __attribute__((ext_vector_type(8)));
+    bool over = false;   // a value above 1 or +inf (bit patterns above 1.0's): not an occupancy probability
     for (int k = tid; k < kSPY * 4 * kChunks; k += blockDim.x) {
         const int r = k / (4 * kChunks), rem = k % (4 * kChunks);
         const int sx = rem / kChunks, ch = rem % kChunks;
         const int y = y0 + r;
         const int xq = q0 + 8 * ch;
         if (y >= Hqp || xq >= pl.Wq4) continue;
-        gstore((s8*)(out + ((y & 3) * 4 + sx) * pl.sub4 + (long long)(y >> 2) * pl.Wq4 + xq), *(const s8*)&hs[r][sx][8 * ch]);
+        const s8 v = *(const s8*)&hs[r][sx][8 * ch];
+        const b8 bits = __builtin_bit_cast(b8, v);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) over |= bits[i] > 0x3C00u;
+        gstore((s8*)(out + ((y & 3) * 4 + sx) * pl.sub4 + (long long)(y >> 2) * pl.Wq4 + xq), v);
     }
+    // as the 8-bit units do (quad_u8): the set's bounds are disabled
+    if (over && job.negflag) gstore(job.negflag, job.pgen);
 }
 
 // --------------------------------------------------------------------------

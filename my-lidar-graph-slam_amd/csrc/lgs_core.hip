@@ -991,13 +991,13 @@ __global__ __launch_bounds__(256) void k_precompute_planes(const PrecompJob* __r
             if (j.out16) {   // the pair's fp16 round-ups (o is even: 4-byte aligned)
                 gstore((unsigned*)(j.out16 + o),
                        (unsigned)half_round_up_bits(ma) | ((unsigned)half_round_up_bits(mb) << 16));
-                if (ma < 0.0 || mb < 0.0) gstore(j.negflag, j.pgen);
+                if (!(ma >= 0.0) || !(mb >= 0.0)) gstore(j.negflag, j.pgen);   // negative or NaN
             }
         } else {
             gstore(dst, ma);
             if (j.out16) {
                 gstore(j.out16 + o, half_round_up_bits(ma));
-                if (ma < 0.0) gstore(j.negflag, j.pgen);
+                if (!(ma >= 0.0)) gstore(j.negflag, j.pgen);   // negative or NaN
             }
         }
     }
@@ -1141,13 +1141,13 @@ __global__ __launch_bounds__(256) void k_precompute_planes_s(const PrecompJob* _
                 if (j.out16) {
                     gstore((unsigned*)(j.out16 + o),
                            (unsigned)half_round_up_bits(ma) | ((unsigned)half_round_up_bits(mb) << 16));
-                    if (ma < 0.0 || mb < 0.0) gstore(j.negflag, j.pgen);
+                    if (!(ma >= 0.0) || !(mb >= 0.0)) gstore(j.negflag, j.pgen);   // negative or NaN
                 }
             } else {
                 gstore(dst, ma);
                 if (j.out16) {
                     gstore(j.out16 + o, half_round_up_bits(ma));
-                    if (ma < 0.0) gstore(j.negflag, j.pgen);
+                    if (!(ma >= 0.0)) gstore(j.negflag, j.pgen);   // negative or NaN
                 }
             }
         }
