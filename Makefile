@@ -24,6 +24,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_loop_sq
 	$(MAKE) -C tests/cpp_pgcg
 	$(MAKE) -C tests/cpp_pglm
+	$(MAKE) -C tests/cpp_icp
 
 clean:
 	$(MAKE) -C my-lidar-graph-slam_amd/csrc clean
@@ -38,5 +39,6 @@ clean:
 	$(MAKE) -C tests/cpp_loop_sq clean
 	$(MAKE) -C tests/cpp_pgcg clean
 	$(MAKE) -C tests/cpp_pglm clean
+	$(MAKE) -C tests/cpp_icp clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean

@@ -1022,6 +1022,87 @@ int  lgs_pg_lm_linearize(lgs_ctx* ctx, int loss_kind, double loss_scale, double 
 int  lgs_pg_lm_stats(const lgs_ctx* ctx, long long* optimizes, long long* steps, long long* pose_uploads,
                      long long* pose_downloads, long long* incidence_builds);
 
+/* ---- point-to-line ICP: one scan matched against another (k_icp.hip) ----
+ * The reference has no scan-to-scan matcher, so the algorithm is the project's
+ * own and DESIGN.md 4.5b states it statement for statement; a test-side
+ * restatement (tests/icp_oracle.py) and the device agree byte for byte.  In
+ * short: every usable beam of the reference scan gives a point q_j at the
+ * reference sensor pose and, with its nearer usable neighbour j-1 / j+1 no
+ * farther than max_segment_length, a unit normal; every usable beam of the
+ * current scan is paired with its nearest q_j (brute force, ties to the lowest
+ * j) if that lies within max_correspondence_dist and has a normal; the
+ * point-to-line residuals give the Gauss-Newton normal equations, solved with
+ * the linear solver's column-pivoting QR, in OptimizePose's loop shape.  All
+ * arithmetic is fp64 without contraction, sin/cos are glibc's sincos, and every
+ * sum is a fixed tree of the beam count alone, so a refine gives the same bytes
+ * in every run, on every context, alone or in a batch.
+ * A beam is usable iff !(r >= hi || r <= lo), lo = max(usable_range_min, scan
+ * min_range), hi = min(usable_range_max, scan max_range).
+ * LGS_ERR_INVALID_ARG, before any device work: a NULL argument (trajectory
+ * apart), n < 0, a parameter or pose that is not finite,
+ * max_correspondence_dist <= 0 or max_segment_length <= 0, a negative
+ * regularizer, an empty scan, more than 4096 usable reference beams (the table
+ * lives in LDS).  An angle outside the restated sincos domain
+ * (|theta + angle| >= 105414350) fails with LGS_ERR_INTERNAL.  A failing call
+ * writes nothing to its outputs. */
+typedef struct {
+    int    num_iterations_max;        /* at least one step runs whatever this is */
+    double convergence_threshold;
+    double usable_range_min, usable_range_max;
+    double translation_regularizer, rotation_regularizer;
+    double max_correspondence_dist;
+    double max_segment_length;
+} lgs_icp_params;
+
+typedef struct {
+    int pose_found;               /* 0 when a pass paired fewer than 3 beams */
+    int iterations;               /* steps made */
+    int num_pairs;                /* pairs of the last pass */
+    int initial_pairs;            /* pairs at the initial pose */
+    double normalized_cost;       /* cost / NumOfScans() */
+    lgs_pose2d initial_pose;
+    lgs_pose2d estimated_pose;    /* MoveBackward(best_sensor_pose, relPose) */
+    /* inv(H + diag(regularizers)) by the closed-form adjugate, scaled by
+     * pair_cost / max(1, num_pairs - 3); all zero when pose_found == 0 or the
+     * determinant is 0 or not finite.  With A = H + diag, row-major a0..a8:
+     *   c00 = a4*a8 - a5*a7   c01 = a2*a7 - a1*a8   c02 = a1*a5 - a2*a4
+     *   c10 = a5*a6 - a3*a8   c11 = a0*a8 - a2*a6   c12 = a2*a3 - a0*a5
+     *   c20 = a3*a7 - a4*a6   c21 = a1*a6 - a0*a7   c22 = a0*a4 - a1*a3
+     *   det = (a0*c00 + a1*c10) + a2*c20
+     *   covariance[3r+c] = (c_rc / det) * (pair_cost / max(1, num_pairs - 3)) */
+    double covariance[9];
+    lgs_pose2d sensor_pose;       /* Compound(initial_pose, relPose) */
+    lgs_pose2d best_sensor_pose;  /* the last pose */
+    double cost;                  /* last pass: e^2 per pair, max_correspondence_dist^2 per usable unpaired beam */
+    double pair_cost;             /* last pass: e^2 per pair */
+    double initial_cost;
+    double hessian[9];            /* last pass's H, row-major, without the regularizers */
+    double rhs[3];                /* last pass's b = sum of (-e) g */
+} lgs_icp_summary;
+size_t lgs_icp_params_size(void);    /* sizeof, for bindings */
+size_t lgs_icp_summary_size(void);
+
+/* One refine of `scan` from initial_pose (robot poses; the sensor poses are
+ * Compound(pose, the scan's relative sensor pose)) against ref_scan at
+ * ref_pose.  trajectory (may be NULL; room for 5 * max(1, num_iterations_max)
+ * doubles) receives after every step the sensor pose (x, y, theta), the cost
+ * at it and the pairs there (as a double). */
+int  lgs_icp_optimize_pose(lgs_ctx* ctx, const lgs_scan* ref_scan, lgs_pose2d ref_pose, const lgs_scan* scan,
+                           lgs_pose2d initial_pose, const lgs_icp_params* params, lgs_icp_summary* out,
+                           double* trajectory);
+/* n refines, item j: scans[j] from initial_poses[j] against ref_scans[j] at
+ * ref_poses[j]; pointers may repeat, scans may differ in size.  One workgroup
+ * per item, one launch per chunk (4096 items), one synchronisation per call.
+ * Equal to n lone calls byte for byte. */
+int  lgs_icp_optimize_pose_batch(lgs_ctx* ctx, const lgs_scan* const* ref_scans, const lgs_pose2d* ref_poses,
+                                 const lgs_scan* const* scans, const lgs_pose2d* initial_poses, int n,
+                                 const lgs_icp_params* params, lgs_icp_summary* out);
+/* Diagnostics: the search alone at one *sensor* pose of `scan`.  Per beam of
+ * `scan`: index[i] = the paired reference beam j*, -1 for a usable beam that
+ * was rejected, -2 for an unusable one; residual[i] = e for a pair, else 0. */
+int  lgs_icp_pairs(lgs_ctx* ctx, const lgs_scan* ref_scan, lgs_pose2d ref_pose, const lgs_scan* scan,
+                   lgs_pose2d sensor_pose, const lgs_icp_params* params, int* index, double* residual);
+
 #ifdef __cplusplus
 }
 #endif

@@ -458,6 +458,44 @@ ScanMatchingSummary ScanMatcherLinearSolverHip::OptimizePose(const ScanMatchingQ
     return o;
 }
 
+// ---------------------------------------------- ScanMatcherIcpPointToLineHip
+ScanMatcherIcpPointToLineHip::ScanMatcherIcpPointToLineHip(DevicePtr dev, const IcpPointToLineParams& p)
+    : mDev(std::move(dev))
+{
+    mParams = { p.mNumOfIterationsMax, p.mConvergenceThreshold, p.mUsableRangeMin, p.mUsableRangeMax,
+                p.mTranslationRegularizer, p.mRotationRegularizer, p.mMaxCorrespondenceDist, p.mMaxSegmentLength };
+}
+
+void ScanMatcherIcpPointToLineHip::SetReference(ScanDataPtr refScan, const RobotPose2D<double>& refPose)
+{
+    mRefScan = std::move(refScan);
+    mRefPose = refPose;
+}
+
+ScanMatchingSummary ScanMatcherIcpPointToLineHip::OptimizePose(const ScanDataPtr& refScan,
+                                                               const RobotPose2D<double>& refPose,
+                                                               const ScanDataPtr& scan,
+                                                               const RobotPose2D<double>& initialPose)
+{
+    if (!refScan || !scan) throw Error(LGS_ERR_INVALID_ARG, "ScanMatcherIcpPointToLineHip: null scan");
+    mDev->Check(lgs_icp_optimize_pose(mDev->Handle(), refScan->Handle(), to_c(refPose), scan->Handle(),
+                                      to_c(initialPose), &mParams, &mLast, nullptr),
+                "lgs_icp_optimize_pose");
+    ScanMatchingSummary o;
+    o.mPoseFound = mLast.pose_found != 0;
+    o.mNormalizedCost = mLast.normalized_cost;
+    o.mInitialPose = from_c(mLast.initial_pose);
+    o.mEstimatedPose = from_c(mLast.estimated_pose);
+    o.mEstimatedCovariance = cov_of(mLast.covariance);
+    return o;
+}
+
+ScanMatchingSummary ScanMatcherIcpPointToLineHip::OptimizePose(const ScanMatchingQuery& q)
+{
+    if (!mRefScan) throw Error(LGS_ERR_INVALID_ARG, "ScanMatcherIcpPointToLineHip: no reference scan set");
+    return OptimizePose(mRefScan, mRefPose, q.mScanData, q.mInitialPose);
+}
+
 // --------------------------------------------------------------- GridMapHip
 GridMapHip::GridMapHip(DevicePtr dev, double resolution, int patchSize, int numCellsX, int numCellsY,
                        const RobotPose2D<double>& c)

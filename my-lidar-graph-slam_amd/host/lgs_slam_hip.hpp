@@ -22,6 +22,8 @@
 //     (C/mapping/loop_detector_grid_search.cpp:26-106)     LoopDetectorGridSearchHip
 //   ScanMatcherHillClimbing (H/mapping/scan_matcher_hill_climbing.hpp)
 //                                                           ScanMatcherHillClimbingHip
+//   (no counterpart: a scan matched against another scan)
+//                                                           ScanMatcherIcpPointToLineHip
 //
 // Everything is a thin RAII layer over the C-ABI (include/lgs_hip.h); the
 // compute runs in HIP kernels on the GPU.  Value types are self-contained
@@ -381,6 +383,39 @@ private:
     DevicePtr mDev;
     lgs_linsolve_params mParams{};
     lgs_linsolve_summary mLast{};
+};
+
+// Point-to-line ICP: a scan matched against another scan (lgs_icp_*,
+// DESIGN.md §4.5b).  The reference has no such matcher; the parameter order
+// follows ScanMatcherLinearSolver's constructor, then the two ICP distances.
+struct IcpPointToLineParams {
+    int mNumOfIterationsMax = 50;
+    double mConvergenceThreshold = 1e-6;
+    double mUsableRangeMin = 0.01, mUsableRangeMax = 20.0;
+    double mTranslationRegularizer = 1e-3, mRotationRegularizer = 1e-3;
+    double mMaxCorrespondenceDist = 1.0;
+    double mMaxSegmentLength = 0.5;
+};
+
+class ScanMatcherIcpPointToLineHip final : public ScanMatcher {
+public:
+    ScanMatcherIcpPointToLineHip(DevicePtr dev, const IcpPointToLineParams& params);
+    // the scan later queries are matched against, and its robot pose
+    void SetReference(ScanDataPtr refScan, const RobotPose2D<double>& refPose);
+    ScanMatchingSummary OptimizePose(const ScanDataPtr& refScan, const RobotPose2D<double>& refPose,
+                                     const ScanDataPtr& scan, const RobotPose2D<double>& initialPose);
+    // the query's scan against the reference (the query's grid map is not
+    // read); Error(LGS_ERR_INVALID_ARG) when no reference has been set
+    ScanMatchingSummary OptimizePose(const ScanMatchingQuery& queryInfo) override;
+    const lgs_icp_summary& LastSummary() const { return mLast; }
+    const lgs_icp_params& Params() const { return mParams; }
+
+private:
+    DevicePtr mDev;
+    lgs_icp_params mParams{};
+    ScanDataPtr mRefScan;
+    RobotPose2D<double> mRefPose;
+    lgs_icp_summary mLast{};
 };
 
 // GridMap<BinaryBayesGridCell<double>> with cells on the device and the

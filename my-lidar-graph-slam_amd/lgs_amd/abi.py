@@ -215,6 +215,22 @@ class LinsolveSummary(C.Structure):
                 ("sensor_pose", Pose2D), ("best_sensor_pose", Pose2D), ("cost", C.c_double)]
 
 
+class IcpParams(C.Structure):
+    """lgs_icp_params: the point-to-line ICP matcher."""
+    _fields_ = [("num_iterations_max", C.c_int), ("convergence_threshold", C.c_double),
+                ("usable_range_min", C.c_double), ("usable_range_max", C.c_double),
+                ("translation_regularizer", C.c_double), ("rotation_regularizer", C.c_double),
+                ("max_correspondence_dist", C.c_double), ("max_segment_length", C.c_double)]
+
+
+class IcpSummary(C.Structure):
+    _fields_ = [("pose_found", C.c_int), ("iterations", C.c_int), ("num_pairs", C.c_int), ("initial_pairs", C.c_int),
+                ("normalized_cost", C.c_double), ("initial_pose", Pose2D), ("estimated_pose", Pose2D),
+                ("covariance", C.c_double * 9), ("sensor_pose", Pose2D), ("best_sensor_pose", Pose2D),
+                ("cost", C.c_double), ("pair_cost", C.c_double), ("initial_cost", C.c_double),
+                ("hessian", C.c_double * 9), ("rhs", C.c_double * 3)]
+
+
 class LoopQuery(C.Structure):
     _fields_ = [("map", C.c_void_p), ("coarse", C.c_void_p), ("local_map_node_pose", Pose2D),
                 ("local_map_node_index", C.c_int), ("first_candidate", C.c_int), ("num_candidates", C.c_int)]
@@ -431,6 +447,14 @@ _PROTOS = [
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("lgs_pg_lm_stats", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                   C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    ("lgs_icp_params_size", C.c_size_t, []),
+    ("lgs_icp_summary_size", C.c_size_t, []),
+    ("lgs_icp_optimize_pose", C.c_int, [_P, _P, Pose2D, _P, Pose2D, C.POINTER(IcpParams), C.POINTER(IcpSummary),
+                                        C.POINTER(C.c_double)]),
+    ("lgs_icp_optimize_pose_batch", C.c_int, [_P, C.POINTER(_P), C.POINTER(Pose2D), C.POINTER(_P), C.POINTER(Pose2D),
+                                              C.c_int, C.POINTER(IcpParams), C.POINTER(IcpSummary)]),
+    ("lgs_icp_pairs", C.c_int, [_P, _P, Pose2D, _P, Pose2D, C.POINTER(IcpParams), C.POINTER(C.c_int),
+                                C.POINTER(C.c_double)]),
     ("lgs_debug_keysort", C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
     ("lgs_debug_map_rebuilds", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("lgs_debug_copy_counters", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -920,6 +944,41 @@ class Context:
         self.check(self.lib.lgs_linsolve_optimize_pose_batch(self.h, grid.h, C.byref(params), arr, poses, n, out),
                    "linsolve_optimize_pose_batch")
         return list(out)
+
+    # ---- point-to-line ICP (scan against scan) ----
+    def icp(self, ref_scan, ref_pose, scan, init, params: "IcpParams", trajectory: bool = False):
+        """lgs_icp_optimize_pose; returns the summary and, with trajectory=True,
+        [(x, y, theta, cost, pairs)] after every step."""
+        out = IcpSummary()
+        traj = np.zeros(5 * max(1, params.num_iterations_max)) if trajectory else None
+        self.check(self.lib.lgs_icp_optimize_pose(self.h, ref_scan.h, Pose2D(*ref_pose), scan.h, Pose2D(*init),
+                                                  C.byref(params), C.byref(out), dptr(traj) if trajectory else None),
+                   "icp_optimize_pose")
+        if trajectory:
+            return out, [tuple(traj[5 * k: 5 * k + 5]) for k in range(out.iterations)]
+        return out
+
+    def icp_batch(self, ref_scans, ref_poses, scans, inits, params: "IcpParams"):
+        n = len(scans)
+        rarr = (_P * max(1, n))(*[s.h for s in ref_scans])
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        rposes = (Pose2D * max(1, n))(*[Pose2D(*p) for p in ref_poses])
+        poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in inits])
+        out = (IcpSummary * max(1, n))()
+        self.check(self.lib.lgs_icp_optimize_pose_batch(self.h, rarr, rposes, sarr, poses, n, C.byref(params), out),
+                   "icp_optimize_pose_batch")
+        return list(out)[:n]
+
+    def icp_pairs(self, ref_scan, ref_pose, scan, sensor_pose, params: "IcpParams"):
+        """lgs_icp_pairs: (index, residual) per beam of `scan` at a sensor pose;
+        index is the paired reference beam, -1 rejected, -2 unusable."""
+        n = len(scan.ranges)
+        index = np.zeros(n, dtype=np.int32)
+        residual = np.zeros(n)
+        self.check(self.lib.lgs_icp_pairs(self.h, ref_scan.h, Pose2D(*ref_pose), scan.h, Pose2D(*sensor_pose),
+                                          C.byref(params), index.ctypes.data_as(C.POINTER(C.c_int)), dptr(residual)),
+                   "icp_pairs")
+        return index, residual
 
     def cost_square_error(self, grid, umin: float, umax: float, scan, sensor_pose, covariance: bool = False):
         v = C.c_double()

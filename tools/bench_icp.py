@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""Point-to-line ICP matcher (lgs_icp_*) on config 3's shape:
+1081-beam scans, 50 steps, convergence threshold 0, a scan matched against the
+scan taken a short way off.  K4's linear solver (lgs_linsolve_*, the matcher
+config 3 measures) runs in the same process on the same scans for scale.
+
+Prints one JSON line per measurement:
+  lone    lgs_icp_optimize_pose: p50 / p90 of the call (the host clock around
+          a call that ends in a synchronisation), steps and pairs
+  batch   lgs_icp_optimize_pose_batch of 256 refines: refines/s, time per refine
+  k4      lgs_linsolve_optimize_pose (lone p50 / p90) and _batch of 256
+
+The GPU measurements run in one child process under a time limit; a child that
+fails or times out ends the run.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "my-lidar-graph-slam_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+ICP = (50, 0.0, 0.01, 20.0, 1e-3, 1e-3, 1.0, 0.5)
+LINSOLVE = (50, 0.0, 0.01, 20.0, 1e-3, 1e-3, 0.01, 20.0)
+BATCH = 256
+
+
+def pct(t, q):
+    return round(float(np.percentile(1e6 * np.array(t), q)), 1)
+
+
+def gpu_step(args):
+    import oracle_bind as ob
+    from lgs_amd import abi, scene
+    world = scene.make_world()
+    ang = scene.beam_angles(args.beams)
+    rng = np.random.default_rng(11)
+    items = []
+    for _ in range(BATCH):
+        ref = (rng.uniform(-0.8, 0.8), rng.uniform(-0.8, 0.8), rng.uniform(-np.pi, np.pi))
+        true = (ref[0] + rng.uniform(-0.2, 0.2), ref[1] + rng.uniform(-0.2, 0.2), ref[2] + rng.uniform(-0.05, 0.05))
+        init = (true[0] + rng.uniform(-0.05, 0.05), true[1] + rng.uniform(-0.05, 0.05), true[2] + rng.uniform(-0.03, 0.03))
+        items.append((ref, true, init))
+    ctx = abi.Context(0)
+    refs = [ctx.scan(scene.ray_cast(world, r, ang), ang) for r, _, _ in items]
+    scans = [ctx.scan(scene.ray_cast(world, t, ang), ang) for _, t, _ in items]
+    ref_poses, inits = [r for r, _, _ in items], [i for _, _, i in items]
+    P = abi.IcpParams(*ICP)
+    for k in range(args.warmup):
+        ctx.icp(refs[k], ref_poses[k], scans[k], inits[k], P)
+    lone, outs = [], []
+    for k in range(args.lone):
+        t0 = time.perf_counter()
+        o = ctx.icp(refs[k], ref_poses[k], scans[k], inits[k], P)
+        lone.append(time.perf_counter() - t0)
+        outs.append(o)
+    err = [float(np.hypot(o.estimated_pose.x - items[k][1][0], o.estimated_pose.y - items[k][1][1]))
+           for k, o in enumerate(outs)]
+    print(json.dumps(dict(line="lone", matcher="icp", calls=len(lone), beams=len(ang), settings=list(ICP),
+                          p50_us=pct(lone, 50), p90_us=pct(lone, 90),
+                          steps_mean=round(float(np.mean([o.iterations for o in outs])), 2),
+                          pairs_mean=round(float(np.mean([o.num_pairs for o in outs])), 1),
+                          found=int(sum(o.pose_found for o in outs)),
+                          p50_us_per_pass=round(pct(lone, 50) / (ICP[0] + 1), 2),
+                          median_error_m=float(np.median(err)))), flush=True)
+    call = lambda: ctx.icp_batch(refs, ref_poses, scans, inits, P)
+    for _ in range(args.warmup):
+        call()
+    t = []
+    for _ in range(args.steps):
+        t0 = time.perf_counter()
+        out = call()
+        t.append(time.perf_counter() - t0)
+    wall = float(np.median(t))
+    print(json.dumps(dict(line="batch", matcher="icp", refines=BATCH, beams=len(ang), call_ms=round(1e3 * wall, 3),
+                          refines_per_s=round(BATCH / wall, 1), us_per_refine=round(1e6 * wall / BATCH, 2),
+                          found=int(sum(o.pose_found for o in out)))), flush=True)
+    # K4 on a map of the same scene, the same current scans and starts
+    m = ob.OMap(0.05, 100, 300, 300)
+    bp = ob.BuilderParams(0.01, 20.0, 0.6, 0.45)
+    mang = scene.beam_angles(361)
+    for p in scene.arc_poses(10):
+        m.integrate(p, ob.OScan(scene.ray_cast(world, p, mang), mang), bp)
+    g = ctx.grid_from_array(m.cells(), m.m.min_x, m.m.min_y, 0.05)
+    L = abi.LinsolveParams(*LINSOLVE)
+    for k in range(args.warmup):
+        ctx.linsolve(g, L, scans[k], inits[k])
+    lone = []
+    for k in range(args.lone):
+        t0 = time.perf_counter()
+        ctx.linsolve(g, L, scans[k], inits[k])
+        lone.append(time.perf_counter() - t0)
+    call = lambda: ctx.linsolve_batch(g, L, scans, inits)
+    for _ in range(args.warmup):
+        call()
+    t = []
+    for _ in range(args.steps):
+        t0 = time.perf_counter()
+        call()
+        t.append(time.perf_counter() - t0)
+    wall = float(np.median(t))
+    print(json.dumps(dict(line="k4", matcher="linsolve", calls=len(lone), beams=len(ang), settings=list(LINSOLVE),
+                          p50_us=pct(lone, 50), p90_us=pct(lone, 90), batch_refines=BATCH,
+                          batch_call_ms=round(1e3 * wall, 3), batch_us_per_refine=round(1e6 * wall / BATCH, 2))),
+          flush=True)
+    ctx.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--beams", type=int, default=1081)
+    ap.add_argument("--lone", type=int, default=32, help="lone calls timed")
+    ap.add_argument("--steps", type=int, default=5, help="timed batch calls")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--timeout", type=float, default=240.0, help="time limit of the GPU step (s)")
+    ap.add_argument("--step", choices=["gpu"], help=argparse.SUPPRESS)   # child mode
+    args = ap.parse_args()
+    if args.step:
+        gpu_step(args)
+        return 0
+    cmd = [sys.executable, os.path.abspath(__file__), "--step", "gpu", "--beams", str(args.beams), "--lone",
+           str(args.lone), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    try:
+        rc = subprocess.run(cmd, timeout=args.timeout).returncode
+    except subprocess.TimeoutExpired:
+        print(json.dumps(dict(line="gpu", error="timeout")), flush=True)
+        return 124
+    if rc != 0:
+        print(json.dumps(dict(line="gpu", error=f"exit status {rc}")), flush=True)
+        return rc if rc > 0 else 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
