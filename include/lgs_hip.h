@@ -194,11 +194,12 @@ int  lgs_abi_version(void);
 #define LGS_OPT_SPLIT_CHUNKS  30  /* A/B: 1 = a correlative call of 32..64 matches runs as two chunks of half the size (the two buffer banks overlap); 0 (default) = one chunk per 64 */
 #define LGS_OPT_DEVICE_HITS   31  /* 1 (default) = lgs_maps_construct_from_scans / lgs_map_construct_global form the hit points (glibc sincos restated), boxes, ray cells and key offsets on the device; 0 = on the host */
 #define LGS_OPT_SEED_WIDE     32  /* batches: the pruning bound seeded from the best members of this many candidate superblocks (5..16, default 12; the 4 best members fine-scored); 0..4 = 4 candidates in one launch */
-#define LGS_OPT_ZERO_TILES    33  /* 1 (default) = the per-map passes of a correlative batch skip the stores of a tile whose inputs are all +0 when that set's buffer already holds the tile's +0 outputs (per-tile words kept per bank, set and layout); 0 = every tile stored */
+#define LGS_OPT_ZERO_TILES    33  /* 1 (default) = the per-map passes of a correlative batch skip the stores of a tile whose inputs are all +0 when that set's buffer already holds the tile's +0 outputs (the precompute: one word per tile; the superblock pass k_super_hv: one bit per thread, a 64-bit word per set, plane and wave; kept per bank, set and layout); 0 = everything stored */
 #define LGS_OPT_DEVICE_TIMING 34  /* 1 = while LGS_OPT_PROFILE(_MASK) times a kernel of a correlative batch chunk, time it on the device instead of with stream events: its workgroups stamp s_memrealtime (100 MHz) at start and end into per-chunk words (two relaxed atomic maxima per workgroup), copied back with the chunk's records; a launch's time is its first workgroup's start to its last workgroup's end (the execution span rocprofv3 reports, not the wait of a stream event for the CUs).  Launches outside a chunk's main chain keep event timing.  0 (default) = events */
 #define LGS_OPT_LEAN_PROJECT  35  /* 1 (default) = batched pruned correlative chunks (work list, wide seed, staged fine evaluation) write only the superblock base of every (angle, beam) plus per-beam / per-angle trig tables, and the kernels that stage a coarse-base or cell row form it themselves with the projection's own arithmetic (bit-identical); 0 = every row materialised (the guard fix-up reruns and lone matches always materialise) */
 #define LGS_OPT_PGCG_GRID_NODES 36 /* lgs_pg_cg_solve: systems of at least this many nodes run over many workgroups, two launches per CG pass (default 1280: up to there the vectors of the one-workgroup solve fit LDS and it is the faster one); smaller ones in one persistent workgroup.  0 = always the grid, 2^31 - 1 = never */
 #define LGS_OPT_FAST_ROWS     37  /* 1 (default) = a lean batch's superblock pass forms a wave's 64 hit-point cells with a shorter fp64 chain (csrc/fast_cell.hpp) wherever every lane's cell is certified equal to the exact chain's and unguarded, and with the exact chain otherwise (bit-identical records); 0 = the exact chain always */
+#define LGS_OPT_HV_INZERO     38  /* 1 (default) = a thread of the superblock pass (k_super_hv) whose whole input footprint lies in precompute tiles that read all-(+0) inputs this call (k_hv_inzero: one 64-bit lane mask per set and wave) issues none of its loads; 0 = no mask, every thread loads (A/B inside one build, tests).  Batches of two or more maps only (a lone call is latency-bound and takes no mask); needs LGS_OPT_ZERO_TILES 1 */
 #define LGS_OPT_POISON_WS     15/* diagnostics: 1 = fill every match workspace and record with 0xFF bytes before the batch runs (any read-before-write shows up) */
 int  lgs_ctx_set_option(lgs_ctx* ctx, int option, double value);
 
@@ -208,7 +209,11 @@ int  lgs_ctx_set_option(lgs_ctx* ctx, int option, double value);
  * 3 Lp at byte 0, Lc[4] f64 at byte 64, 4 tedge [T i32] (1 = flagged by
  * the last enqueue of item 0, else 0), 5 cbase [2*(T*Nv+pad) i32],
  * 6 idx [T*Nv int2], 7 cscore [K f64], 8 coarse phase planes [lr*lr planes
- * of Hqp x Wqp f64, DESIGN.md §2], 9 superblock planes [fp16]. */
+ * of Hqp x Wqp f64, DESIGN.md §2], 9 superblock planes [fp16], 10 the
+ * in-masks of the item's set after the last batch [one u64 per wave of a
+ * plane's k_super_hv threads: bit l = lane l loaded nothing; empty when the set
+ * had none], 11 its out-masks [lr*lr planes x waves u64: bit l = everything
+ * lane l stores holds +0; empty without LGS_OPT_ZERO_TILES]. */
 int  lgs_debug_item_buffer(lgs_ctx* ctx, int item, int which, void* out, size_t cap, size_t* bytes);
 
 /* Diagnostics: the device's restatements of glibc's sincos() (op 0: out[2i] =

@@ -35,6 +35,7 @@
 //               table terms, beam-order sums; no guards, no host fix-up).
 #include "lgs_internal.hpp"
 #include "fast_cell.hpp"
+#include "hv_zero.hpp"
 #include "sq_cost_stage.hpp"
 #include "ge_cost_device.hpp"
 
@@ -162,7 +163,9 @@ struct PlaneJob {
     RtcsmPlan pl;            // layout fields (Wqp, Hqp, pstride, pstride4, sub4, Wq4)
     const unsigned short* planes16;   // the planes rounded up to fp16 (same layout)
     SuperT* super;
-    unsigned* zt;   // k_super_hv's zero-tile words of this set (null: none), see ZeroTiles
+    unsigned long long* zt;        // k_super_hv's out-masks of this set (null: none), see ZeroTiles
+    unsigned long long* inz;       // its in-masks, written by k_hv_inzero this call (null: every thread loads)
+    const unsigned* ptz;           // the zero-tile words this call's precompute keeps for the set (with inz)
     int* negflag;   // stamped with pgen when a bound value exceeds 1 (8-bit units cannot hold it)
     int pgen;
 };
@@ -1302,6 +1305,13 @@ struct SuperGeom {
 };
 // k_super_hv's grid (x): workgroups per plane
 inline int hv_grid_x(const SuperGeom& g, int nq) { return (g.ncol * (g.nqt + nq - 1) + 255) / 256; }
+// thread slot tq of a plane is (qi, c) = (tq / ncol, tq % ncol) and works on
+// quad (nq = 2: unit) qt0 = qlo + qi - (nq - 1); the slots past the quads, and
+// unit -1, are not live
+__host__ __device__ inline bool hv_live(const SuperGeom& g, int nq, int qi, int qt0)
+{
+    return qi < g.nqt + nq - 1 && qt0 >= 0;
+}
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pkmax(unsigned a, unsigned b)
 {
@@ -1327,15 +1337,19 @@ __global__ __launch_bounds__(256) void k_super_hv(const PlaneJob* __restrict__ j
     const int qi = tq / g.ncol, c = tq - qi * g.ncol;
     // NQ = 2: units qlo - 1 .. qlo + nqt - 1 (unit u holds quads u, u + 1)
     const int qt0 = g.qlo + qi - (NQ - 1);
-    const bool live = qi < g.nqt + NQ - 1 && qt0 >= 0 && c < g.ncol;
-    // zero tiles (ZeroTiles): the workgroup's word says whether every unit
-    // half it stores holds +0 from its previous build; threads past the
-    // quads then load in-range rows and take part in the barrier only
-    unsigned* zw = job.zt ? job.zt + ((long long)p * gridDim.x + wg.x) : nullptr;   // uniform
-    if (!live && !zw) return;
-    const int X4 = g.X4lo + min(c, g.ncol - 1), qt = min(max(qt0, 0), g.qlo + g.nqt - 1);
-    const int rx = p % g.lr, ry = p / g.lr;
+    if (!hv_live(g, NQ, qi, qt0)) return;
+    // zero tiles (ZeroTiles), per thread: bit `lane` of the (plane, wave)'s
+    // out-mask says that everything this thread stores holds +0 from its
+    // previous build, bit `lane` of the (set, wave)'s in-mask (k_hv_inzero)
+    // that every cell it would load is +0 in every plane of this call
     typedef unsigned long long u64;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tq >> 6), nwv = 4 * (int)gridDim.x;
+    u64* zw = job.zt ? job.zt + ((long long)p * nwv + wave) : nullptr;   // uniform per wave
+    const u64 zprev = zw ? *zw : 0ull;   // read by every lane before any of them rewrites it (below)
+    const bool inz = job.inz && ((job.inz[wave] >> lane) & 1ull);
+    const int X4 = g.X4lo + c, qt = qt0;
+    const int rx = p % g.lr, ry = p / g.lr;
     typedef const __attribute__((address_space(1))) u64 gu64_t;
     typedef const __attribute__((address_space(1))) unsigned short gu16_t;
     const unsigned short* P = job.planes16;
@@ -1346,52 +1360,60 @@ __global__ __launch_bounds__(256) void k_super_hv(const PlaneJob* __restrict__ j
     // every load first, from always-valid addresses (rows past the plane
     // clamped to its last row, then zeroed; the strip column's value loaded
     // by every thread, from its own row where it is not the strip): a load
-    // under a branch made the compiler wait for each row (19 round trips)
-    u64 la[NR], lb[NR];
-    unsigned short ls[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const int Y = min(16 * qt + k, g.Hqp - 1);
-        const bool rs = (Y == g.M - 1) && ry > 0;            // the row strip
-        const unsigned short* row = rs ? P + rx * g.pstride + rowM : P + p * g.pstride + (long long)Y * g.Wqp;
-        // column M - 1 reads column M of plane (0, ry) (row strip: plane 0)
-        const unsigned short* src = !cstrip ? row + 4 * X4
-                                  : rs ? P + rowM + g.M : P + ry * g.lr * g.pstride + (long long)Y * g.Wqp + g.M;
-        la[k] = *(gu64_t*)(row + 4 * X4);
-        lb[k] = *(gu64_t*)(row + 4 * X4 + 4);
-        ls[k] = *(gu16_t*)src;
-    }
-    u64 hm[NR];   // horizontal forward 4-max of columns 4 X4 + k, k < 4, per row
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const bool in = 16 * qt + k < g.Hqp;
-        u64 a = in ? la[k] : 0ull;
-        const u64 b = in ? lb[k] : 0ull;
-        if (cstrip) a = (a & 0x0000FFFFFFFFFFFFull) | ((u64)(in ? ls[k] : 0) << 48);
-        // columns 0..7 as packed pairs: a = (c0 c1)(c2 c3), b = (c4 c5)(c6 c7)
-        const unsigned a0 = (unsigned)a, a1 = (unsigned)(a >> 32), b0 = (unsigned)b, b1 = (unsigned)(b >> 32);
-        const unsigned m01 = pkmax(a0, (a0 >> 16) | (a1 << 16));   // (max c0c1, max c1c2)
-        const unsigned m23 = pkmax(a1, (a1 >> 16) | (b0 << 16));   // (max c2c3, max c3c4)
-        const unsigned m45 = pkmax(b0, (b0 >> 16) | (b1 << 16));   // (max c4c5, max c5c6)
-        hm[k] = (u64)pkmax(m01, m23) | ((u64)pkmax(m23, m45) << 32);   // 4-max at columns 0, 1 | 2, 3
-    }
+    // under a branch made the compiler wait for each row (19 round trips).
+    // The in-mask's branch is ONE branch around all 3 NR loads and the maxima:
+    // a lane it skips takes zeros, as its loads would have returned.
     unsigned vlo[16 * NQ], vhi[16 * NQ];   // vertical forward 4-max
+    unsigned nzw = 0;
+    if (!inz) {
+        u64 la[NR], lb[NR];
+        unsigned short ls[NR];
 #pragma unroll
-    for (int k = 0; k < 16 * NQ; ++k) {
-        vlo[k] = pkmax(pkmax((unsigned)hm[k], (unsigned)hm[k + 1]), pkmax((unsigned)hm[k + 2], (unsigned)hm[k + 3]));
-        vhi[k] = pkmax(pkmax((unsigned)(hm[k] >> 32), (unsigned)(hm[k + 1] >> 32)),
-                       pkmax((unsigned)(hm[k + 2] >> 32), (unsigned)(hm[k + 3] >> 32)));
+        for (int k = 0; k < NR; ++k) {
+            const int Y = min(16 * qt + k, g.Hqp - 1);
+            const bool rs = (Y == g.M - 1) && ry > 0;            // the row strip
+            const unsigned short* row = rs ? P + rx * g.pstride + rowM : P + p * g.pstride + (long long)Y * g.Wqp;
+            // column M - 1 reads column M of plane (0, ry) (row strip: plane 0)
+            const unsigned short* src = !cstrip ? row + 4 * X4
+                                      : rs ? P + rowM + g.M : P + ry * g.lr * g.pstride + (long long)Y * g.Wqp + g.M;
+            la[k] = *(gu64_t*)(row + 4 * X4);
+            lb[k] = *(gu64_t*)(row + 4 * X4 + 4);
+            ls[k] = *(gu16_t*)src;
+        }
+        u64 hm[NR];   // horizontal forward 4-max of columns 4 X4 + k, k < 4, per row
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const bool in = 16 * qt + k < g.Hqp;
+            u64 a = in ? la[k] : 0ull;
+            const u64 b = in ? lb[k] : 0ull;
+            if (cstrip) a = (a & 0x0000FFFFFFFFFFFFull) | ((u64)(in ? ls[k] : 0) << 48);
+            // columns 0..7 as packed pairs: a = (c0 c1)(c2 c3), b = (c4 c5)(c6 c7)
+            const unsigned a0 = (unsigned)a, a1 = (unsigned)(a >> 32), b0 = (unsigned)b, b1 = (unsigned)(b >> 32);
+            const unsigned m01 = pkmax(a0, (a0 >> 16) | (a1 << 16));   // (max c0c1, max c1c2)
+            const unsigned m23 = pkmax(a1, (a1 >> 16) | (b0 << 16));   // (max c2c3, max c3c4)
+            const unsigned m45 = pkmax(b0, (b0 >> 16) | (b1 << 16));   // (max c4c5, max c5c6)
+            hm[k] = (u64)pkmax(m01, m23) | ((u64)pkmax(m23, m45) << 32);   // 4-max at columns 0, 1 | 2, 3
+        }
+#pragma unroll
+        for (int k = 0; k < 16 * NQ; ++k) {
+            vlo[k] = pkmax(pkmax((unsigned)hm[k], (unsigned)hm[k + 1]), pkmax((unsigned)hm[k + 2], (unsigned)hm[k + 3]));
+            vhi[k] = pkmax(pkmax((unsigned)(hm[k] >> 32), (unsigned)(hm[k + 1] >> 32)),
+                           pkmax((unsigned)(hm[k + 2] >> 32), (unsigned)(hm[k + 3] >> 32)));
+            nzw |= vlo[k] | vhi[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16 * NQ; ++k) vlo[k] = vhi[k] = 0u;
     }
     if (zw) {
-        unsigned nzw = 0;
-#pragma unroll
-        for (int k = 0; k < 16 * NQ; ++k) nzw |= vlo[k] | vhi[k];
-        const unsigned zprev = *zw;                            // read by every thread before the
-        const int anynz = __syncthreads_or(live && nzw != 0);  // barrier, rewritten after it
-        if (!anynz && zprev == 1u) return;
-        if (threadIdx.x == 0 && zprev != (anynz ? 0u : 1u)) *zw = anynz ? 0u : 1u;
+        // the wave's ballot of "all my values are +0" becomes the new word
+        // (lanes that left above: 0); a zero lane whose old bit was set has
+        // nothing to store.  zprev feeds the condition of the one store, so
+        // every lane's read of the word is complete before it is rewritten.
+        const u64 zero = __ballot(nzw == 0);
+        if (zero != zprev && lane == __builtin_amdgcn_readfirstlane(lane)) *zw = zero;
+        if (nzw == 0 && ((zprev >> lane) & 1ull)) return;
     }
-    if (!live) return;
     // 8-bit units of unit8 dwords: a quad's 4 rows are dword 0 of unit qt,
     // dword 1 of unit qt - 1 (and dword 2 of unit qt - 2)
     unsigned* __restrict__ uo = (unsigned*)job.super + (long long)g.unit8 * p * g.pstrideO;
@@ -1423,6 +1445,46 @@ __global__ __launch_bounds__(256) void k_super_hv(const PlaneJob* __restrict__ j
         }
     }
     if (over && job.negflag) gstore(job.negflag, job.pgen);
+}
+
+// k_hv_inzero: k_super_hv's in-masks, once per call (not per plane), after the
+// precompute: one thread per (set, thread slot of a plane), grid (workgroups
+// per plane, 1, sets).  A thread ANDs "word == 1" over the precompute tiles
+// its k_super_hv loads can depend on (hv_zero.hpp) -- a tile's word is 1 when
+// this call's precompute read an all-(+0) footprint for it, so its plane and
+// fp16 outputs are +0 in every plane -- and the wave's ballot is the mask.
+// Sets without such words (job.inz null) are left alone.
+__global__ __launch_bounds__(256) void k_hv_inzero(const PlaneJob* __restrict__ jobs, SuperGeom g, int nq, HvTiling til,
+                                                   DevTs dts)
+{
+    const DtsScope dts_scope(dts);
+    const PlaneJob& job = jobs[blockIdx.z];
+    if (!job.inz) return;   // uniform
+    const int tq = blockIdx.x * 256 + threadIdx.x;
+    const int qi = tq / g.ncol, c = tq - qi * g.ncol;
+    const int qt0 = g.qlo + qi - (nq - 1);
+    bool z = false;
+    if (hv_live(g, nq, qi, qt0)) {
+        const HvTileRange r = hv_zero_range(qt0, g.X4lo + c, nq, g.M, job.pl.Wq, job.pl.Hq, g.lr, til);
+        // up to ~26 words (13 tile rows x 2 tile columns), 16 loads in flight
+        // at a time (indices past the range repeat its last tile): the
+        // kernel is nothing but the latency of these loads
+        const int ntx = r.tx1 - r.tx0 + 1, nt = r.empty() ? 0 : (r.ty1 - r.ty0 + 1) * ntx;
+        unsigned bad = 0;
+        for (int i0 = 0; i0 < nt; i0 += 16) {
+            unsigned w[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int i = min(i0 + k, nt - 1), dy = i / ntx;
+                w[k] = job.ptz[(r.ty0 + dy) * til.pgx + r.tx0 + (i - dy * ntx)];
+            }
+#pragma unroll
+            for (int k = 0; k < 16; ++k) bad |= w[k] != 1u;
+        }
+        z = bad == 0;
+    }
+    const unsigned long long m = __ballot(z);
+    if ((threadIdx.x & 63) == 0) job.inz[tq >> 6] = m;
 }
 
 // k_super: one workgroup (kSupWaves waves) per (chunk of superblocks, search
@@ -4556,6 +4618,10 @@ struct PlaneSet {
     int pgen = 0;
     bool half_copy = false;             // the fp16 copy comes from k_planes16 (not the precompute)
     unsigned short* planes16 = nullptr;
+    // k_super_hv's lane masks of this set after the batch (lgs_debug_item_buffer; null: none)
+    const unsigned long long* hv_in = nullptr;
+    const unsigned long long* hv_out = nullptr;
+    size_t hv_in_bytes = 0, hv_out_bytes = 0;
 };
 
 // Build the coarse maps of every set: batched precompute straight into the
@@ -4564,6 +4630,8 @@ struct PlaneSet {
 struct SetJobs {
     size_t jobs_off = 0, njobs = 0, pj_off = 0, npj = 0, dj_off = 0, ndj = 0;
     bool hv = false;   // k_super_hv (else k_super_planes)
+    bool inz = false;  // some set takes in-masks: k_hv_inzero runs, over the precompute tiling til
+    HvTiling til{};
 };
 
 // k_super_hv applies: octet unit layout (else k_super_planes)
@@ -4592,23 +4660,44 @@ SuperGeom super_geom(const RtcsmPlan& lp)
 // map's room covers 23% of its 1000 x 1000 cells), and the per-map passes
 // write every plane, fp16 copy and superblock unit of it again for each
 // query.  k_precompute_planes (the launch's tiling: 16-row tiles, a lone
-// map's shorter ones) and k_super_hv keep one
-// word per tile / workgroup and set: 1 = the outputs it stores were built
-// from all-(+0) inputs, so they hold +0; a tile whose inputs are still all +0
-// then stores nothing -- the same bits, without the writes.  The words are
-// kept valid here, per bank: a change of the plane layout, of a launch grid
-// or of a buffer clears them all (0 = build the tile), and a set whose planes
-// or units another path writes is marked stale, its words cleared before
-// their next use.  (Only writers that keep the words write the tiles they
-// cover; the zeroing of a whole buffer keeps them true.)
-void zero_tiles(lgs_ctx* ctx, const RtcsmPlan& lp, const std::vector<PlaneSet>& sets, std::vector<PrecompJob>& jobs,
-                const std::vector<int>& job_set, std::vector<PlaneJob>& pj, double* D, SuperT* S, bool need_super)
+// map's shorter ones) keeps one word per tile and set: 1 = the outputs it
+// stores were built from all-(+0) inputs, so they hold +0; a tile whose inputs
+// are still all +0 then stores nothing -- the same bits, without the writes.
+// k_super_hv keeps the same per THREAD (a workgroup spans the map's width, so
+// a word per workgroup never saw an all-zero input on a map with a room in
+// it): one 64-bit out-mask per set, plane and wave of its thread index space,
+// bit l = everything lane l stores holds +0 from its previous build.  A lane
+// whose maxima are all 0 and whose bit is set stores nothing; the wave's
+// ballot replaces the word when it differs.  The words and masks are kept
+// valid here, per bank: a change of the plane layout, of a launch grid, of the
+// word layout or of a buffer clears them all (0 = build), and a set whose
+// planes or units another path writes is marked stale, its words cleared
+// before their next use.  (Only writers that keep the words write the tiles
+// they cover; the zeroing of a whole buffer keeps them true.)
+//
+// In-masks (LGS_OPT_HV_INZERO): the precompute's words of THIS call also say
+// which fp16 cells are +0 before k_super_hv reads them.  k_hv_inzero turns
+// them into one 64-bit mask per set and wave (hv_zero.hpp maps a thread's
+// footprint to the tiles it can depend on, the same for every plane); a lane
+// whose bit is set issues no load and takes zeros -- a maximum of +0 values is
+// +0, so no value changes.  The masks are rebuilt by every call that uses
+// them and carry no state; sets whose planes this call's precompute did not
+// write with words (k_planes16 copies, supplied coarse maps, odd sizes, no
+// zero tiles) get a null mask and load everything, and so does a lone map
+// (one job): its call is bound by launch latency, not by this pass.
+void zero_tiles(lgs_ctx* ctx, const RtcsmPlan& lp, std::vector<PlaneSet>& sets, std::vector<PrecompJob>& jobs,
+                const std::vector<int>& job_set, std::vector<PlaneJob>& pj, double* D, SuperT* S, bool need_super,
+                HvTiling* til, bool* any_in)
 {
     const int b = ctx->bank, ns = (int)sets.size(), lr = lp.low_res;
     std::vector<unsigned char>& pre_ok = ctx->zt_pre[b];
     std::vector<unsigned char>& hv_ok = ctx->zt_hv[b];
     if ((int)pre_ok.size() < ns) pre_ok.resize(ns, 0);
     if ((int)hv_ok.size() < ns) hv_ok.resize(ns, 0);
+    for (auto& ps : sets) {
+        ps.hv_in = ps.hv_out = nullptr;
+        ps.hv_in_bytes = ps.hv_out_bytes = 0;
+    }
     const bool want = ctx->zero_tiles && need_super && lr <= 8 && hv_mode(ctx, lp);
     const bool use_pre = want && !jobs.empty();
     const bool use_hv = want;
@@ -4625,14 +4714,26 @@ void zero_tiles(lgs_ctx* ctx, const RtcsmPlan& lp, const std::vector<PlaneSet>& 
     const SuperGeom g = super_geom(lp);
     const int nq = ctx->hv_full && lp.unit8 == 2 ? 2 : 1;
     const int hgx = hv_grid_x(g, nq);
-    const long long pre_words = use_pre ? (long long)pgx * pgy : 0;
-    const long long hv_words = use_hv ? (long long)lr * lr * hgx : 0;
-    const long long per_set = pre_words + hv_words;
+    // per set, in 32-bit words: the precompute's tile words (an even count:
+    // the 64-bit masks follow), k_super_hv's out-masks (one 64-bit word per
+    // plane and wave of its thread index space) and, where this call's
+    // precompute keeps words for the set, its in-masks (one per wave)
+    // (not for a lone map: its call is latency-bound, and the extra launch cost
+    // more than the skipped loads saved -- lone p50 0.132 -> 0.144 ms)
+    const bool use_in = use_pre && use_hv && ctx->hv_inzero && jobs.size() > 1;
+    const int nwv = 4 * hgx;   // waves of a plane's threads (256-thread workgroups)
+    const long long pre_words = use_pre ? ((long long)pgx * pgy + 1) / 2 * 2 : 0;
+    const long long hv_words = use_hv ? 2LL * lr * lr * nwv : 0;
+    const long long in_words = use_in ? 2LL * nwv : 0;
+    const long long per_set = pre_words + hv_words + in_words;
+    *til = HvTiling{ pgx, pgy, prows, hv_pcols(lr), 0, 0 };
+    *any_in = false;
     if (per_set > 0) {
         unsigned* Z = (unsigned*)ctx->ensure(ctx->banked(S_ZTILE), sizeof(unsigned) * (size_t)(per_set * ns));
-        const long long key[12] = { (long long)(uintptr_t)D, (long long)(uintptr_t)S, (long long)(uintptr_t)Z,
+        const long long key[13] = { (long long)(uintptr_t)D, (long long)(uintptr_t)S, (long long)(uintptr_t)Z,
                                     lr, lp.Wq, lp.Hq, lp.M * 16 + lp.oct * 4 + lp.unit8, lp.pstride,
-                                    pgx, (long long)pgy << 8 | prows, hgx, nq };
+                                    pgx, (long long)pgy << 8 | prows, hgx, nq,
+                                    (long long)nwv << 8 | (use_in ? 16 : 0) | 2 /* lane masks */ };
         if (std::memcmp(key, ctx->zt_key[b], sizeof(key)) != 0) {
             std::memcpy(ctx->zt_key[b], key, sizeof(key));
             std::fill(pre_ok.begin(), pre_ok.end(), 0);
@@ -4647,11 +4748,22 @@ void zero_tiles(lgs_ctx* ctx, const RtcsmPlan& lp, const std::vector<PlaneSet>& 
             clear |= !ok;
             jobs[k].zt = Z + per_set * s;
             pre_now[s] = 1;
+            if (use_in) {   // the set's planes and fp16 copies are this precompute's, with words
+                pj[s].ptz = jobs[k].zt;
+                pj[s].inz = (unsigned long long*)(Z + per_set * s + pre_words + hv_words);
+                til->W = jobs[k].W;   // (the maps of one batch share their size)
+                til->H = jobs[k].H;
+                *any_in = true;
+                sets[s].hv_in = pj[s].inz;
+                sets[s].hv_in_bytes = sizeof(unsigned) * (size_t)in_words;
+            }
         }
         for (int s = 0; s < ns && use_hv; ++s) {
             clear |= !hv_ok[s];
-            pj[s].zt = Z + per_set * s + pre_words;
+            pj[s].zt = (unsigned long long*)(Z + per_set * s + pre_words);
             hv_now[s] = 1;
+            sets[s].hv_out = pj[s].zt;
+            sets[s].hv_out_bytes = sizeof(unsigned) * (size_t)hv_words;
         }
         // (a cleared word only makes its tile build once more)
         if (clear) LGS_HIP_CHECK(hipMemsetAsync(Z, 0, sizeof(unsigned) * (size_t)(per_set * ns), ctx->stream));
@@ -4740,7 +4852,9 @@ SetJobs build_sets(lgs_ctx* ctx, const RtcsmPlan& lp, std::vector<PlaneSet>& set
         }
         if (need_super) pj.push_back(j);
     }
-    zero_tiles(ctx, lp, sets, jobs, job_set, pj, D, S, need_super);
+    HvTiling til{};
+    bool any_in = false;
+    zero_tiles(ctx, lp, sets, jobs, job_set, pj, D, S, need_super, &til, &any_in);
     // the descriptors of this step go up with the batch's items (one copy):
     // the caller flushes before calling launch_sets
     SetJobs sj;
@@ -4751,6 +4865,8 @@ SetJobs build_sets(lgs_ctx* ctx, const RtcsmPlan& lp, std::vector<PlaneSet>& set
     sj.ndj = djobs.size();
     sj.dj_off = djobs.empty() ? 0 : up.append(djobs.data(), djobs.size());
     sj.hv = hv_mode(ctx, lp);
+    sj.til = til;
+    sj.inz = any_in;
     return sj;
 }
 
@@ -4792,6 +4908,9 @@ void launch_sets(lgs_ctx* ctx, const RtcsmPlan& lp, const std::vector<PlaneSet>&
         const int tok = ctx->timing_begin(K_SUPER_PLANES, cq * (16.0 * 4.0 * 2.0 + 16.0 * 8.0 * g.unit8));
         if (!ctx->skipped(K_SUPER_PLANES))
         {
+            if (sj.inz)   // the in-masks first, timed with the pass they serve
+                hipLaunchKernelGGL(k_hv_inzero, dim3(grid.x, 1, (unsigned)sj.npj), dim3(256), 0, ctx->stream,
+                                   up.at<PlaneJob>(sj.pj_off), g, nq, sj.til, ctx->dts(tok));
             if (nq == 2)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_super_hv<2>), grid, dim3(256), 0, ctx->stream,
                                    up.at<PlaneJob>(sj.pj_off), np, g, ctx->dts(tok));
@@ -5595,6 +5714,11 @@ void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost
         d.bytes[8] = ij.cmap ? plane_bytes(q) : 0;
         d.buf[9] = ij.super;
         d.bytes[9] = ij.super ? super_bytes(q) : 0;
+        const PlaneSet* dps = B.small ? nullptr : &sets[set_of[j]];   // k_super_hv's lane masks of the item's set
+        d.buf[10] = dps ? dps->hv_in : nullptr;
+        d.bytes[10] = dps ? dps->hv_in_bytes : 0;
+        d.buf[11] = dps ? dps->hv_out : nullptr;
+        d.bytes[11] = dps ? dps->hv_out_bytes : 0;
         d.gen = ij.gen;
     }
     const size_t items_off = up.append(items.data(), items.size());
@@ -5965,7 +6089,7 @@ void cost_summaries(lgs_ctx* ctx, const lgs_grid* grid, const lgs_cost_ge_params
 
 extern "C" int lgs_debug_item_buffer(lgs_ctx* ctx, int item, int which, void* out, size_t cap, size_t* bytes)
 {
-    if (!ctx || which < 0 || which >= 10 || item < 0) return LGS_ERR_INVALID_ARG;
+    if (!ctx || which < 0 || which >= 12 || item < 0) return LGS_ERR_INVALID_ARG;
     return guarded(ctx, [&] {
         LGS_REQUIRE((size_t)item < ctx->dbg.size(), "no such item in the last correlative batch");
         const lgs_ctx::DbgItem& d = ctx->dbg[(size_t)item];

@@ -8,6 +8,7 @@
 // the end when n < w.  Max is exact, so the separable pair equals one 2-D
 // window max over zero-padded input; it is computed here from an LDS tile.
 #include "lgs_internal.hpp"
+#include "hv_zero.hpp"
 
 #include <atomic>
 #include <condition_variable>
@@ -546,6 +547,7 @@ extern "C" int lgs_ctx_set_option(lgs_ctx* ctx, int option, double value)
     case LGS_OPT_SPLIT_CHUNKS: ctx->split_chunks = value != 0.0; return LGS_OK;
     case LGS_OPT_DEVICE_HITS: ctx->device_hits = value != 0.0; return LGS_OK;
     case LGS_OPT_ZERO_TILES: ctx->zero_tiles = value != 0.0; return LGS_OK;
+    case LGS_OPT_HV_INZERO: ctx->hv_inzero = value != 0.0; return LGS_OK;
     case LGS_OPT_LEAN_PROJECT: ctx->lean_project = value != 0.0; return LGS_OK;
     case LGS_OPT_FAST_ROWS: ctx->fast_rows = value != 0.0; return LGS_OK;
     case LGS_OPT_PGCG_GRID_NODES:
@@ -876,6 +878,10 @@ __global__ __launch_bounds__(256) void k_precompute_tiled(const double* __restri
 constexpr int pqx_of(int LR) { return ((257 - LR) / LR) & ~1; }
 template <int LR>
 constexpr int pqx() { return pqx_of(LR); }
+// (hv_zero.hpp maps k_super_hv's footprints to these tiles)
+static_assert(lgs::hv_pcols(1) == pqx_of(1) && lgs::hv_pcols(2) == 2 * pqx_of(2) && lgs::hv_pcols(3) == 3 * pqx_of(3) &&
+              lgs::hv_pcols(4) == 4 * pqx_of(4) && lgs::hv_pcols(5) == 5 * pqx_of(5) && lgs::hv_pcols(6) == 6 * pqx_of(6) &&
+              lgs::hv_pcols(7) == 7 * pqx_of(7) && lgs::hv_pcols(8) == 8 * pqx_of(8), "hv_zero.hpp: columns per precompute tile");
 typedef double d2a16 __attribute__((ext_vector_type(2)));
 template <int LR, int kPTY = 16>
 __global__ __launch_bounds__(256) void k_precompute_planes(const PrecompJob* __restrict__ jobs, DevTs dts)

@@ -352,6 +352,7 @@ struct lgs_ctx {
     bool zero_tiles = true;   // LGS_OPT_ZERO_TILES          // batches: candidate superblocks whose best members seed the bound (LGS_OPT_SEED_WIDE; <= 4: one launch)
     bool device_hits = true;     // map rebuilds of many scans: hit points / ray cells on the device (LGS_OPT_DEVICE_HITS)
     bool split_chunks = false;   // calls of 32..64 matches as two chunks (LGS_OPT_SPLIT_CHUNKS; measured r05, 8-rank loop block: 1.007 vs 0.869 ms as one)
+    bool hv_inzero = true;       // k_super_hv threads with all-(+0) inputs load nothing (LGS_OPT_HV_INZERO, k_hv_inzero)
     bool hv_full = false;        // k_super_hv stores 16-byte units whole (LGS_OPT_HV_FULL, A/B; measured r05: 0.24 vs 0.17 ms per 64 sets)
     // a batch's stages after the coarse-map builds run on `hi`, a stream of
     // the device's highest priority, behind an event on `stream`: the
@@ -376,8 +377,8 @@ struct lgs_ctx {
     bool poison_ws = false;
     // intermediates of every item of the last correlative batch (lgs_debug_item_buffer)
     struct DbgItem {
-        const void* buf[10];
-        size_t bytes[10];
+        const void* buf[12];
+        size_t bytes[12];
         int gen;
     };
     std::vector<DbgItem> dbg;
@@ -448,7 +449,7 @@ struct lgs_ctx {
     long long planes_key[2][4] = { { -1, -1, -1, -1 }, { -1, -1, -1, -1 } };
     // zero-tile words of the per-map passes (k_rtcsm.hip ZeroTiles), per bank:
     // the layout they were kept for and which sets' words are current
-    long long zt_key[2][12] = {};
+    long long zt_key[2][13] = {};
     std::vector<unsigned char> zt_pre[2], zt_hv[2];
     std::vector<long long> zt_dims[2];   // per set: W << 32 | H of the map its precompute words describe
     double* zero = nullptr;      // 32 zero doubles: target of out-of-map gathers

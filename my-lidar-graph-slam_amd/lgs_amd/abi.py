@@ -48,6 +48,7 @@ LGS_OPT_DEVICE_TIMING = 34   # correlative chunks' kernels timed on the device (
 LGS_OPT_LEAN_PROJECT = 35    # batched chunks: only superblock bases projected; consumers form their rows
 LGS_OPT_PGCG_GRID_NODES = 36  # lgs_pg_cg_solve: node count from which the solve runs over many workgroups
 LGS_OPT_FAST_ROWS = 37       # lean batches: certified fast hit-point cells in the superblock pass (0: exact chain)
+LGS_OPT_HV_INZERO = 38       # k_super_hv: threads whose inputs the precompute found all +0 load nothing (0: all load)
 KERNEL_IDS = ["k_project", "k_coarse", "k_seed", "k_select", "k_fine", "k_replay", "k_cost", "k_precompute",
               "k_linsolve", "k_ray_emit", "k_ray_apply", "k_super", "k_super_planes", "k_bb_score",
               "k_bb_expand", "k_coarse_aux", "k_match_small", "k_gs_score",
@@ -1187,7 +1188,8 @@ class Context:
 
     DEBUG_BUFFERS = {"sbound": (0, np.float64), "part_c": (1, np.float64), "part_k": (2, np.int64),
                      "L": (3, np.float64), "tedge": (4, np.int32), "cbase": (5, np.int32), "idx": (6, np.int32),
-                     "cscore": (7, np.float64), "planes": (8, np.float64), "super": (9, np.float16)}
+                     "cscore": (7, np.float64), "planes": (8, np.float64), "super": (9, np.float16),
+                     "hv_inmask": (10, np.uint64), "hv_outmask": (11, np.uint64)}
 
     def debug_buffer(self, name: str, item: int = 0) -> np.ndarray:
         """Diagnostics: an intermediate buffer of one item of the last
