@@ -25,6 +25,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_pgcg
 	$(MAKE) -C tests/cpp_pglm
 	$(MAKE) -C tests/cpp_icp
+	$(MAKE) -C tests/cpp_icp_ref
 	$(MAKE) -C tests/cpp_hv
 
 clean:
@@ -41,6 +42,7 @@ clean:
 	$(MAKE) -C tests/cpp_pgcg clean
 	$(MAKE) -C tests/cpp_pglm clean
 	$(MAKE) -C tests/cpp_icp clean
+	$(MAKE) -C tests/cpp_icp_ref clean
 	$(MAKE) -C tests/cpp_hv clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean

@@ -1108,6 +1108,57 @@ int  lgs_icp_optimize_pose_batch(lgs_ctx* ctx, const lgs_scan* const* ref_scans,
 int  lgs_icp_pairs(lgs_ctx* ctx, const lgs_scan* ref_scan, lgs_pose2d ref_pose, const lgs_scan* scan,
                    lgs_pose2d sensor_pose, const lgs_icp_params* params, int* index, double* residual);
 
+/* ---- point-to-line ICP against a set of reference scans (k_icp_ref.hip) ----
+ * A reference is the table of 4.5b built once from scans R_0 .. R_{K-1} at
+ * robot poses P_k: the table of R_0 at Compound(P_0, rel_0), then that of R_1,
+ * and so on; entries in scan order, then beam order; lines never cross scans;
+ * each scan's usable interval is its own.  An entry's index is its position in
+ * this concatenation.  It lives in global memory behind the handle, together
+ * with a uniform grid over its points.  Pass, sums, tree, loop, summary and
+ * covariance are those of lgs_icp_* over that table: a beam pairs with the
+ * entry of the smallest computed d2 (ties to the lowest index; +inf and NaN
+ * never win) and the pair is accepted iff d2 <= D^2 and the entry has a line.
+ * The grid only changes the order in which entries are looked at (an entry
+ * with d2 <= D^2 always lies in the 3 x 3 cells around the hit point's), so
+ * the bytes are those of the brute-force search, and with one reference scan
+ * those of lgs_icp_optimize_pose / _batch / _pairs.
+ * LGS_ERR_INVALID_ARG, before any device work: a NULL argument (trajectory
+ * apart), n_refs < 1 or > 4096, n < 0, the parameter and pose rules of
+ * lgs_icp_*, an empty scan, more than LGS_ICP_REF_MAX_ENTRIES usable reference
+ * beams in total, a reference of another context, and refine-time params whose
+ * usable_range_min/max, max_segment_length or max_correspondence_dist differ
+ * bitwise from those the reference was created with.  A reference whose beams
+ * are all unusable is legal (an empty table: pose_found = 0).  An angle outside
+ * the restated sincos domain fails with LGS_ERR_INTERNAL, at create for the
+ * reference scans' and at refine for the scan's.  A failing call writes
+ * nothing to its outputs. */
+#define LGS_ICP_REF_MAX_ENTRIES 262144
+typedef struct lgs_icp_ref lgs_icp_ref;
+/* Copies what it needs: the scans may be destroyed afterwards.  The reference
+ * belongs to ctx; like an lgs_grid it owns its device memory and may be
+ * destroyed after its context. */
+int  lgs_icp_ref_create(lgs_ctx* ctx, const lgs_scan* const* ref_scans, const lgs_pose2d* ref_poses, int n_refs,
+                        const lgs_icp_params* params, lgs_icp_ref** out);
+void lgs_icp_ref_destroy(lgs_icp_ref* ref);
+/* Reference scans, table entries, entries with a line, the grid's cells per
+ * axis and its cell side (each may be NULL). */
+int  lgs_icp_ref_info(const lgs_icp_ref* ref, int* n_refs, int* entries, int* lines, int* cells_x, int* cells_y,
+                      double* cell_size);
+/* lgs_icp_optimize_pose against the reference */
+int  lgs_icp_ref_optimize_pose(lgs_ctx* ctx, const lgs_icp_ref* ref, const lgs_scan* scan, lgs_pose2d initial_pose,
+                               const lgs_icp_params* params, lgs_icp_summary* out, double* trajectory);
+/* n refines, item j: scans[j] from initial_poses[j] against refs[j]; pointers
+ * may repeat.  Equal to n lone calls byte for byte. */
+int  lgs_icp_ref_optimize_pose_batch(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs_scan* const* scans,
+                                     const lgs_pose2d* initial_poses, int n, const lgs_icp_params* params,
+                                     lgs_icp_summary* out);
+/* The search alone at one *sensor* pose.  Per beam of `scan`: for a pair the
+ * reference scan ref_index[i] = k and its beam beam_index[i] = j; -1 / -1 for
+ * a usable beam that was rejected, -2 / -2 for an unusable one; residual[i] =
+ * e for a pair, else 0. */
+int  lgs_icp_ref_pairs(lgs_ctx* ctx, const lgs_icp_ref* ref, const lgs_scan* scan, lgs_pose2d sensor_pose,
+                       const lgs_icp_params* params, int* ref_index, int* beam_index, double* residual);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,75 +25,20 @@
 //           the stopping rule and the 3x3 column-pivoting QR solve
 //           (solve3_device.hpp) and hands the new pose back through LDS.
 // No atomics: a refine's bytes depend on its inputs alone.
-#include "lgs_internal.hpp"
-#include "glibc_math.hpp"
-#include "icp_host.hpp"
-#include "solve3_device.hpp"
+// The hit point, the line rule of a table entry, the pass with its tree, the
+// stopping rule and the solve live in icp_device.hpp, shared with
+// k_icp_ref.hip (a set of reference scans, the table in global memory behind
+// a grid); this file keeps the LDS table and the brute-force search.
+#include "icp_device.hpp"
 
-#include <cfloat>
-#include <cmath>
-#include <cstring>
 #include <vector>
 
 using namespace lgs;
 
 namespace {
 
-constexpr int kIcpThreads = 1024;
-constexpr int kIcpWaves = kIcpThreads / 64;
-constexpr int kIcpSums = 11;      // cost, pair_cost, H upper triangle (6), b (3)
 constexpr int kIcpUnroll = 8;     // table entries per search trip
 constexpr int kIcpChunk = 4096;   // items per launch
-
-struct IcpItem {
-    const double* r_ranges;
-    const double* r_angles;
-    const double* s_ranges;
-    const double* s_angles;
-    double rpose[3];     // Compound(ref pose, ref scan's relPose), glibc on the host
-    double rlo, rhi;     // usable range of the reference scan
-    double spose[3];     // Compound(initial pose, scan's relPose)
-    double slo, shi;
-    double* traj;        // lone call: 5 doubles per step (null: none)
-    int rn, sn;
-};
-
-struct IcpShared {
-    double conv, reg_t, reg_r;
-    double D2, S2;       // max_correspondence_dist^2, max_segment_length^2 (host products)
-    int max_iter;
-    int cap;             // table entries in LDS, a multiple of kIcpUnroll
-};
-
-struct IcpRecord {
-    double pose[3];
-    double sums[kIcpSums];   // the last pass
-    double initial_cost;
-    int pairs, initial_pairs, iterations, found;
-};
-
-struct IcpStatic {
-    double wsum[kIcpWaves][kIcpSums + 1];
-    int wcnt[kIcpWaves];
-    double pose[3];
-    int stop;
-};
-
-__device__ __forceinline__ bool icp_dev_usable(double r, double lo, double hi) { return !(r >= hi || r <= lo); }
-
-// ScanData::HitPoint of beam j at `pose`
-__device__ __forceinline__ void icp_hit(const double pose[3], double r, double a, double& hx, double& hy, double& rc,
-                                        double& rs, int* __restrict__ err)
-{
-    const double th = pose[2] + a;
-    if (!glm::gl_sincos_ok(th) && th - th == 0.0) *err = 1;   // a finite angle outside the restated domain
-    double sn, cs;
-    glm::gl_sincos(th, &sn, &cs);
-    rc = r * cs;
-    rs = r * sn;
-    hx = pose[0] + rc;
-    hy = pose[1] + rs;
-}
 
 // The reference table of one item into LDS; returns the number of entries
 // (usable beams, at most cap).  orig (kOrig) receives each entry's beam index.
@@ -109,39 +54,8 @@ __device__ int icp_build_table(const IcpItem& it, double S2, int cap, double2* _
         const int j = j0 + (int)threadIdx.x;
         bool us = false;
         double qx = 0.0, qy = 0.0, nx = nan, ny = nan;
-        if (j < it.rn) {
-            const double r = gload(it.r_ranges + j);
-            us = icp_dev_usable(r, it.rlo, it.rhi);
-            if (us) {
-                double rc, rs;
-                icp_hit(it.rpose, r, gload(it.r_angles + j), qx, qy, rc, rs, err);
-                // the line: j - 1 first, then j + 1; the smaller l2, a tie to j - 1
-                bool have = false;
-                double bux = 0.0, buy = 0.0, bl2 = 0.0;
-#pragma unroll
-                for (int side = 0; side < 2; ++side) {
-                    const int k = side ? j + 1 : j - 1;
-                    if (k < 0 || k >= it.rn) continue;
-                    const double rk = gload(it.r_ranges + k);
-                    if (!icp_dev_usable(rk, it.rlo, it.rhi)) continue;
-                    double kx, ky;
-                    icp_hit(it.rpose, rk, gload(it.r_angles + k), kx, ky, rc, rs, err);
-                    const double ux = kx - qx, uy = ky - qy;
-                    const double l2 = ux * ux + uy * uy;
-                    if (l2 > 0.0 && l2 <= S2 && (!have || l2 < bl2)) {
-                        have = true;
-                        bux = ux;
-                        buy = uy;
-                        bl2 = l2;
-                    }
-                }
-                if (have) {
-                    const double l = sqrt(bl2);
-                    nx = (-buy) / l;
-                    ny = bux / l;
-                }
-            }
-        }
+        if (j < it.rn)
+            us = icp_table_entry(it.r_ranges, it.r_angles, it.rn, it.rpose, it.rlo, it.rhi, S2, j, qx, qy, nx, ny, err);
         const unsigned long long bal = __ballot(us);
         if (lane == 0) wcnt[wid] = __popcll(bal);
         __syncthreads();
@@ -211,67 +125,6 @@ __device__ __forceinline__ int icp_pair(const IcpItem& it, double D2, const doub
     return jb;
 }
 
-// One pass at `pose`: thread 0 returns the eleven sums and the pair count.
-// Ends with a barrier behind thread 0's reads of L.wsum.
-__device__ __forceinline__ void icp_pass(const IcpItem& it, const IcpShared& sh, const double pose[3],
-                                         const double2* __restrict__ q, const double2* __restrict__ nrm, int m8,
-                                         IcpStatic& L, double (&out)[kIcpSums], int& out_pairs, int* __restrict__ err)
-{
-    double a[kIcpSums];
-#pragma unroll
-    for (int k = 0; k < kIcpSums; ++k) a[k] = 0.0;
-    int np = 0;
-    for (int i = threadIdx.x; i < it.sn; i += kIcpThreads) {
-        double e, rc, rs;
-        double2 n;
-        const int j = icp_pair(it, sh.D2, pose, i, q, nrm, m8, e, n, rc, rs, err);
-        if (j == -2) continue;
-        if (j == -1) {
-            a[0] = a[0] + sh.D2;
-            continue;
-        }
-        const double g0 = n.x, g1 = n.y, g2 = n.x * (-rs) + n.y * rc;
-        const double ee = e * e, me = -e;
-        a[0] = a[0] + ee;
-        a[1] = a[1] + ee;
-        a[2] = a[2] + g0 * g0;
-        a[3] = a[3] + g0 * g1;
-        a[4] = a[4] + g0 * g2;
-        a[5] = a[5] + g1 * g1;
-        a[6] = a[6] + g1 * g2;
-        a[7] = a[7] + g2 * g2;
-        a[8] = a[8] + me * g0;
-        a[9] = a[9] + me * g1;
-        a[10] = a[10] + me * g2;
-        ++np;
-    }
-#pragma unroll
-    for (int mask = 32; mask >= 1; mask >>= 1) {
-#pragma unroll
-        for (int k = 0; k < kIcpSums; ++k) a[k] = a[k] + __shfl_xor(a[k], mask, 64);
-        np += __shfl_xor(np, mask, 64);
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kIcpSums; ++k) L.wsum[wid][k] = a[k];
-        L.wcnt[wid] = np;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int pairs = L.wcnt[0];
-#pragma unroll
-        for (int k = 0; k < kIcpSums; ++k) out[k] = L.wsum[0][k];
-        for (int w = 1; w < kIcpWaves; ++w) {
-#pragma unroll
-            for (int k = 0; k < kIcpSums; ++k) out[k] = out[k] + L.wsum[w][k];
-            pairs += L.wcnt[w];
-        }
-        out_pairs = pairs;
-    }
-    __syncthreads();
-}
-
 extern __shared__ __attribute__((aligned(16))) unsigned char icp_dyn[];
 
 __global__ __launch_bounds__(kIcpThreads) void k_icp(const IcpItem* __restrict__ items, IcpShared sh,
@@ -284,71 +137,10 @@ __global__ __launch_bounds__(kIcpThreads) void k_icp(const IcpItem* __restrict__
     const int m = icp_build_table<false>(it, sh.S2, sh.cap, q, nrm, nullptr, L.wcnt, err);
     const int m8 = (m + kIcpUnroll - 1) & ~(kIcpUnroll - 1);
 
-    double pose[3] = { it.spose[0], it.spose[1], it.spose[2] };
-    double s[kIcpSums];
-    int pairs = 0;
-    // thread 0's loop state
-    double prevCost = DBL_MAX, initial_cost = 0.0;
-    int iterations = 0, found = 1, initial_pairs = 0;
-    for (int pass = 0;; ++pass) {
-        icp_pass(it, sh, pose, q, nrm, m8, L, s, pairs, err);
-        if (threadIdx.x == 0) {
-            int stop = 0;
-            if (pass == 0) {
-                initial_cost = s[0];
-                initial_pairs = pairs;
-            } else {
-                ++iterations;
-                if (it.traj) {
-                    double* tr = it.traj + (size_t)(iterations - 1) * 5;
-                    tr[0] = pose[0];
-                    tr[1] = pose[1];
-                    tr[2] = pose[2];
-                    tr[3] = s[0];
-                    tr[4] = (double)pairs;
-                }
-            }
-            if (pairs < 3) {
-                found = 0;
-                stop = 1;
-            } else if (pass > 0) {
-                if (iterations >= sh.max_iter || fabs(prevCost - s[0]) < sh.conv) stop = 1;
-                prevCost = s[0];
-            }
-            if (!stop) {
-                const double H[9] = { s[2] + sh.reg_t, s[3], s[4],
-                                      s[3], s[5] + sh.reg_t, s[6],
-                                      s[4], s[6], s[7] + sh.reg_r };
-                const double b[3] = { s[8], s[9], s[10] };
-                double d[3];
-                solve3_colpiv_qr(H, b, d);
-                L.pose[0] = pose[0] + d[0];
-                L.pose[1] = pose[1] + d[1];
-                L.pose[2] = pose[2] + d[2];
-            }
-            L.stop = stop;
-        }
-        __syncthreads();
-        if (L.stop) break;
-        pose[0] = L.pose[0];
-        pose[1] = L.pose[1];
-        pose[2] = L.pose[2];
-        // (the next pass's first barrier stands between these reads and thread 0's next writes)
-    }
-    if (threadIdx.x == 0) {
-        IcpRecord rec;
-        rec.pose[0] = pose[0];
-        rec.pose[1] = pose[1];
-        rec.pose[2] = pose[2];
-#pragma unroll
-        for (int k = 0; k < kIcpSums; ++k) rec.sums[k] = s[k];
-        rec.initial_cost = initial_cost;
-        rec.pairs = pairs;
-        rec.initial_pairs = initial_pairs;
-        rec.iterations = iterations;
-        rec.found = found;
-        recs[blockIdx.x] = rec;
-    }
+    icp_refine(it, sh, L, recs + blockIdx.x,
+               [&](const double pose[3], int i, double& e, double2& n, double& rc, double& rs) {
+                   return icp_pair(it, sh.D2, pose, i, q, nrm, m8, e, n, rc, rs, err);
+               });
 }
 
 // the search alone at it.spose: index / residual per beam of the current scan
@@ -371,7 +163,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_icp_pairs(IcpItem it, IcpShared
 }
 
 // ------------------------------------------------------------------ host
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline size_t align256(size_t b) { return icp_align256(b); }
 
 template <class K>
 void icp_allow_lds(K kernel, size_t bytes)
@@ -381,19 +173,6 @@ void icp_allow_lds(K kernel, size_t bytes)
         (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         (void)hipGetLastError();
     }
-}
-
-IcpShared icp_shared(const lgs_icp_params* p)
-{
-    IcpShared sh;
-    std::memset(&sh, 0, sizeof(sh));
-    sh.conv = p->convergence_threshold;
-    sh.reg_t = p->translation_regularizer;
-    sh.reg_r = p->rotation_regularizer;
-    sh.D2 = p->max_correspondence_dist * p->max_correspondence_dist;
-    sh.S2 = p->max_segment_length * p->max_segment_length;
-    sh.max_iter = p->num_iterations_max;
-    return sh;
 }
 
 // the item without its device pointers, and the reference's usable count
@@ -486,27 +265,7 @@ void run_icp(lgs_ctx* ctx, const lgs_scan* const* refs, const lgs_pose2d* ref_po
         throw Error(LGS_ERR_INTERNAL, "icp: an angle lies outside the restated sincos domain");
     const IcpRecord* rec = (const IcpRecord*)pin;
     for (int j = 0; j < n; ++j) {
-        const IcpRecord& r = rec[j];
-        lgs_icp_summary& o = out[j];
-        std::memset(&o, 0, sizeof(o));
-        o.pose_found = r.found;
-        o.iterations = r.iterations;
-        o.num_pairs = r.pairs;
-        o.initial_pairs = r.initial_pairs;
-        o.cost = r.sums[0];
-        o.pair_cost = r.sums[1];
-        o.initial_cost = r.initial_cost;
-        o.normalized_cost = o.cost / (double)scans[j]->n;
-        o.initial_pose = init[j];
-        o.sensor_pose = sensor[(size_t)j];
-        o.best_sensor_pose = { r.pose[0], r.pose[1], r.pose[2] };
-        o.estimated_pose = move_backward(o.best_sensor_pose, scans[j]->rel);
-        const double H[9] = { r.sums[2], r.sums[3], r.sums[4], r.sums[3], r.sums[5], r.sums[6],
-                              r.sums[4], r.sums[6], r.sums[7] };
-        std::memcpy(o.hessian, H, sizeof(H));
-        for (int k = 0; k < 3; ++k) o.rhs[k] = r.sums[8 + k];
-        icp_covariance(H, p->translation_regularizer, p->rotation_regularizer, o.pair_cost, o.num_pairs, o.pose_found,
-                       o.covariance);
+        icp_summary_of(rec[j], p, init[j], sensor[(size_t)j], scans[j]->rel, scans[j]->n, out[j]);
     }
     if (traj) std::memcpy(traj, pin + rb, sizeof(double) * 5 * (size_t)out[0].iterations);
 }

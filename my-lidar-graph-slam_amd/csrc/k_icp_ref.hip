@@ -1,0 +1,592 @@
+// k_icp_ref.hip -- point-to-line ICP against a set of reference scans: the
+// table of DESIGN.md 4.5b over scans R_0 .. R_{K-1}, built once on the device,
+// kept in global memory behind an lgs_icp_ref, and searched through a uniform
+// grid that returns the brute-force answer.
+//
+//   build   k_icpref_table   one workgroup per reference scan: icp_table_entry
+//                            per beam, compaction in beam order at the scan's
+//                            base (the host counted the usable beams), the
+//                            scan's bounding box (finite points) and lines
+//           (host)           boxes -> grid geometry (icp_ref_host.hpp)
+//           k_icpref_count   entries per cell (integer atomics)
+//           k_icpref_scan    exclusive prefix: cell starts, row-major cells
+//           k_icpref_scatter the cell-ordered copy of (q, index); the order
+//                            inside a cell is whatever the atomics gave
+//   refine  k_icp_ref        one workgroup of 1024 threads per item for the
+//                            whole loop (icp_refine of icp_device.hpp: the
+//                            pass, the tree, the stopping rule and the solve
+//                            of k_icp.hip).  Thread t owns beams t, t + 1024,
+//                            ...; a beam walks the three rows around its hit
+//                            point's cell, in each the contiguous range of
+//                            cells cx - 1 .. cx + 1, and keeps the
+//                            lexicographic minimum of (d2, index) -- so the
+//                            order inside the cells does not matter and the
+//                            result is a function of the inputs alone.
+//   pairs   k_icp_ref_pairs  the search alone
+#include "icp_device.hpp"
+#include "icp_ref_host.hpp"
+
+#include <memory>
+#include <vector>
+
+using namespace lgs;
+
+namespace {
+
+constexpr int kRefChunk = 4096;   // items per launch
+constexpr int kRefWalk = 4;       // cell entries in flight per search trip
+
+// what the kernels read of a reference
+struct IcpRefDev {
+    const double2* tq;     // table order: points
+    const double2* tn;     //              normals (NaN: no line)
+    const int2* tkj;       //              (reference scan, beam)
+    const double2* cq;     // cell order: points
+    const int* cidx;       //             their table indices
+    const int* starts;     // [cells + 1], row-major cells
+    IcpRefGrid g;
+    int m;
+};
+
+}  // namespace
+
+struct lgs_icp_ref {
+    lgs_ctx* ctx = nullptr;   // creating context (compared, never used after its destruction)
+    int device = 0;
+    IcpRefBound bound{};
+    int n_refs = 0, entries = 0, lines = 0;
+    void* mem_table = nullptr;   // tq, tn, tkj
+    void* mem_cells = nullptr;   // cq, cidx, starts
+    IcpRefDev dev{};
+};
+
+namespace {
+
+struct RefScanJob {
+    const double* ranges;
+    const double* angles;
+    double pose[3];    // Compound(P_k, rel_k), glibc on the host
+    double lo, hi;
+    int n;
+    int base, count;   // the scan's first entry and its usable beams (host count)
+};
+
+struct RefScanBox {
+    double min_x, max_x, min_y, max_y;   // over finite points; min > max: none
+    int lines, pad;
+};
+
+struct IcpRefItem {
+    IcpItem it;        // the current scan's half (r_* unused)
+    IcpRefDev ref;
+};
+
+__global__ __launch_bounds__(kIcpThreads) void k_icpref_table(const RefScanJob* __restrict__ jobs, double S2,
+                                                              double2* __restrict__ tq, double2* __restrict__ tn,
+                                                              int2* __restrict__ tkj, RefScanBox* __restrict__ boxes,
+                                                              int* __restrict__ err)
+{
+    __shared__ int wcnt[kIcpWaves];
+    __shared__ double wbox[kIcpWaves][4];
+    __shared__ int wlines[kIcpWaves];
+    const RefScanJob job = jobs[blockIdx.x];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    double mnx = inf, mxx = -inf, mny = inf, mxy = -inf;
+    int lines = 0, base = 0;
+    for (int j0 = 0; j0 < job.n; j0 += kIcpThreads) {
+        const int j = j0 + (int)threadIdx.x;
+        bool us = false;
+        double qx = 0.0, qy = 0.0, nx = nan, ny = nan;
+        if (j < job.n)
+            us = icp_table_entry(job.ranges, job.angles, job.n, job.pose, job.lo, job.hi, S2, j, qx, qy, nx, ny, err);
+        const unsigned long long bal = __ballot(us);
+        if (lane == 0) wcnt[wid] = __popcll(bal);
+        __syncthreads();
+        int off = base, total = 0;
+#pragma unroll
+        for (int w = 0; w < kIcpWaves; ++w) {
+            const int c = wcnt[w];
+            off += (w < wid) ? c : 0;
+            total += c;
+        }
+        off += __popcll(bal & ((1ull << lane) - 1ull));
+        if (us && off < job.count) {
+            const int e = job.base + off;
+            tq[e] = make_double2(qx, qy);
+            tn[e] = make_double2(nx, ny);
+            tkj[e] = make_int2((int)blockIdx.x, j);
+            if (qx - qx == 0.0 && qy - qy == 0.0) {
+                mnx = fmin(mnx, qx);
+                mxx = fmax(mxx, qx);
+                mny = fmin(mny, qy);
+                mxy = fmax(mxy, qy);
+            }
+            lines += (nx == nx) ? 1 : 0;
+        }
+        base += total;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int mask = 32; mask >= 1; mask >>= 1) {
+        mnx = fmin(mnx, __shfl_xor(mnx, mask, 64));
+        mxx = fmax(mxx, __shfl_xor(mxx, mask, 64));
+        mny = fmin(mny, __shfl_xor(mny, mask, 64));
+        mxy = fmax(mxy, __shfl_xor(mxy, mask, 64));
+        lines += __shfl_xor(lines, mask, 64);
+    }
+    if (lane == 0) {
+        wbox[wid][0] = mnx;
+        wbox[wid][1] = mxx;
+        wbox[wid][2] = mny;
+        wbox[wid][3] = mxy;
+        wlines[wid] = lines;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        RefScanBox b;
+        b.min_x = wbox[0][0];
+        b.max_x = wbox[0][1];
+        b.min_y = wbox[0][2];
+        b.max_y = wbox[0][3];
+        b.lines = wlines[0];
+        b.pad = 0;
+        for (int w = 1; w < kIcpWaves; ++w) {
+            b.min_x = fmin(b.min_x, wbox[w][0]);
+            b.max_x = fmax(b.max_x, wbox[w][1]);
+            b.min_y = fmin(b.min_y, wbox[w][2]);
+            b.max_y = fmax(b.max_y, wbox[w][3]);
+            b.lines += wlines[w];
+        }
+        boxes[blockIdx.x] = b;
+    }
+}
+
+// the row-major cell of a table point, -1: none (a point that is not finite)
+__device__ __forceinline__ int icpref_cell_of(const IcpRefGrid& g, double2 q)
+{
+    const int cx = icp_ref_cell(g.x, q.x), cy = icp_ref_cell(g.y, q.y);
+    if (cx < 0 || cx >= g.x.n || cy < 0 || cy >= g.y.n) return -1;
+    return cy * g.x.n + cx;
+}
+
+__global__ __launch_bounds__(256) void k_icpref_count(const double2* __restrict__ tq, int m, IcpRefGrid g,
+                                                      int* __restrict__ counts)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= m) return;
+    const int c = icpref_cell_of(g, tq[e]);
+    if (c >= 0) atomicAdd(counts + c, 1);
+}
+
+// starts[c] = sum of counts[< c], starts[ncell] = the total; one workgroup,
+// thread t owns the cells [t * chunk, (t + 1) * chunk)
+__global__ __launch_bounds__(kIcpThreads) void k_icpref_scan(const int* __restrict__ counts, int ncell,
+                                                             int* __restrict__ starts)
+{
+    __shared__ int part[kIcpThreads];
+    const int t = threadIdx.x;
+    const int chunk = (ncell + kIcpThreads - 1) / kIcpThreads;
+    const int c0 = min(ncell, t * chunk), c1 = min(ncell, c0 + chunk);
+    int s = 0;
+    for (int c = c0; c < c1; ++c) s += counts[c];
+    part[t] = s;
+    __syncthreads();
+    for (int d = 1; d < kIcpThreads; d <<= 1) {
+        const int v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - s;   // exclusive
+    for (int c = c0; c < c1; ++c) {
+        starts[c] = run;
+        run += counts[c];
+    }
+    if (t == kIcpThreads - 1) starts[ncell] = part[t];
+}
+
+// consumes counts (each cell's falls to 0)
+__global__ __launch_bounds__(256) void k_icpref_scatter(const double2* __restrict__ tq, int m, IcpRefGrid g,
+                                                        const int* __restrict__ starts, int* __restrict__ counts,
+                                                        double2* __restrict__ cq, int* __restrict__ cidx)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= m) return;
+    const double2 q = tq[e];
+    const int c = icpref_cell_of(g, q);
+    if (c < 0) return;
+    const int p = starts[c] + atomicSub(counts + c, 1) - 1;
+    if (p < 0 || p >= m) return;
+    cq[p] = q;
+    cidx[p] = e;
+}
+
+// the lexicographic minimum of (d2, index) over the cells a hit point visits;
+// jb = -1 if nothing there is nearer than +inf
+__device__ __forceinline__ void icpref_search(const IcpRefDev& R, double hx, double hy, double& best, int& jb)
+{
+    best = __longlong_as_double(0x7ff0000000000000LL);
+    jb = -1;
+    int x0, x1, y0, y1;
+    if (!icp_ref_visit(R.g, hx, hy, x0, x1, y0, y1)) return;
+    for (int y = y0; y <= y1; ++y) {
+        const int row = y * R.g.x.n;
+        const int p0 = gload(R.starts + row + x0), p1 = gload(R.starts + row + x1 + 1);
+        for (int p = p0; p < p1; p += kRefWalk) {
+            double2 v[kRefWalk];
+            int id[kRefWalk];
+            // past the range's end the last entry again: it never beats itself
+#pragma unroll
+            for (int u = 0; u < kRefWalk; ++u) {
+                const int pu = min(p + u, p1 - 1);
+                v[u] = gload(R.cq + pu);
+                id[u] = gload(R.cidx + pu);
+            }
+#pragma unroll
+            for (int u = 0; u < kRefWalk; ++u) {
+                const double dx = hx - v[u].x, dy = hy - v[u].y;
+                const double d2 = dx * dx + dy * dy;
+                const bool lt = d2 < best || (d2 == best && id[u] < jb);
+                best = lt ? d2 : best;
+                jb = lt ? id[u] : jb;
+            }
+        }
+    }
+}
+
+// beam i of the current scan at `pose`: -2 unusable, -1 rejected, else the
+// table entry it pairs with (e, n, rc, rs then valid)
+__device__ __forceinline__ int icpref_pair(const IcpItem& it, const IcpRefDev& R, double D2, const double pose[3], int i,
+                                           double& e, double2& n, double& rc, double& rs, int* __restrict__ err)
+{
+    const double r = gload(it.s_ranges + i);
+    if (!icp_dev_usable(r, it.slo, it.shi)) return -2;
+    double hx, hy;
+    icp_hit(pose, r, gload(it.s_angles + i), hx, hy, rc, rs, err);
+    double best;
+    int jb;
+    icpref_search(R, hx, hy, best, jb);
+    if (jb < 0 || !(best <= D2)) return -1;
+    n = gload(R.tn + jb);
+    if (n.x != n.x) return -1;   // no line
+    const double2 p = gload(R.tq + jb);
+    const double dx = hx - p.x, dy = hy - p.y;
+    e = n.x * dx + n.y * dy;
+    return jb;
+}
+
+__global__ __launch_bounds__(kIcpThreads) void k_icp_ref(const IcpRefItem* __restrict__ items, IcpShared sh,
+                                                         IcpRecord* __restrict__ recs, int* __restrict__ err)
+{
+    __shared__ IcpStatic L;
+    const IcpItem it = items[blockIdx.x].it;
+    const IcpRefDev R = items[blockIdx.x].ref;
+    icp_refine(it, sh, L, recs + blockIdx.x,
+               [&](const double pose[3], int i, double& e, double2& n, double& rc, double& rs) {
+                   return icpref_pair(it, R, sh.D2, pose, i, e, n, rc, rs, err);
+               });
+}
+
+// the search alone at it.spose
+__global__ __launch_bounds__(kIcpThreads) void k_icp_ref_pairs(IcpRefItem X, IcpShared sh, int* __restrict__ ref_index,
+                                                               int* __restrict__ beam_index,
+                                                               double* __restrict__ residual, int* __restrict__ err)
+{
+    for (int i = threadIdx.x; i < X.it.sn; i += kIcpThreads) {
+        double e = 0.0, rc, rs;
+        double2 n;
+        const int j = icpref_pair(X.it, X.ref, sh.D2, X.it.spose, i, e, n, rc, rs, err);
+        const int2 kj = j >= 0 ? gload(X.ref.tkj + j) : make_int2(j, j);
+        ref_index[i] = kj.x;
+        beam_index[i] = kj.y;
+        residual[i] = j >= 0 ? e : 0.0;
+    }
+}
+
+// ------------------------------------------------------------------ host
+void icp_ref_free(lgs_icp_ref* r)
+{
+    if (!r) return;
+    // hipFree synchronises with the device; the creating context may already
+    // be gone, so it is not touched here
+    if (r->mem_table || r->mem_cells) {
+        hipSetDevice(r->device);
+        if (r->mem_table) hipFree(r->mem_table);
+        if (r->mem_cells) hipFree(r->mem_cells);
+    }
+    delete r;
+}
+
+struct RefDeleter {
+    void operator()(lgs_icp_ref* r) const { icp_ref_free(r); }
+};
+
+const char* const kSincosMsg = "icp: an angle lies outside the restated sincos domain";
+
+lgs_icp_ref* ref_create(lgs_ctx* ctx, const lgs_scan* const* scans, const lgs_pose2d* poses, int K,
+                        const lgs_icp_params* p)
+{
+    // every check before any device work
+    LGS_REQUIRE(icp_ref_counts_check(K, nullptr) == LGS_OK, "icp ref: 1 .. 4096 reference scans");
+    std::vector<RefScanJob> jobs((size_t)K);
+    std::vector<int> usable((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        LGS_REQUIRE(scans[k], "icp ref: null scan");
+        LGS_REQUIRE(scans[k]->n >= 1, "icp ref: empty scan");
+        LGS_REQUIRE(icp_pose_finite(poses[k]), "icp ref: pose not finite");
+        const lgs_pose2d sp = compound(poses[k], scans[k]->rel);
+        LGS_REQUIRE(icp_pose_finite(sp), "icp ref: pose not finite");
+        RefScanJob& j = jobs[(size_t)k];
+        std::memset(&j, 0, sizeof(j));
+        j.pose[0] = sp.x;
+        j.pose[1] = sp.y;
+        j.pose[2] = sp.theta;
+        j.lo = std::max(p->usable_range_min, scans[k]->min_range);
+        j.hi = std::min(p->usable_range_max, scans[k]->max_range);
+        j.n = scans[k]->n;
+        usable[(size_t)k] = icp_usable_count(scans[k]->h_ranges.data(), scans[k]->n, j.lo, j.hi);
+    }
+    LGS_REQUIRE(icp_ref_counts_check(K, usable.data()) == LGS_OK,
+                "icp ref: more than LGS_ICP_REF_MAX_ENTRIES usable reference beams");
+    int m = 0;
+    for (int k = 0; k < K; ++k) {
+        jobs[(size_t)k].base = m;
+        jobs[(size_t)k].count = usable[(size_t)k];
+        m += usable[(size_t)k];
+    }
+
+    LGS_HIP_CHECK(hipSetDevice(ctx->device));
+    std::unique_ptr<lgs_icp_ref, RefDeleter> ref(new lgs_icp_ref());
+    ref->ctx = ctx;
+    ref->device = ctx->device;
+    ref->bound = icp_ref_bound(p);
+    ref->n_refs = K;
+    ref->entries = m;
+    const size_t mm = (size_t)std::max(m, 1);
+    const size_t qb = icp_align256(sizeof(double2) * mm), kb = icp_align256(sizeof(int2) * mm);
+    if (hipMalloc(&ref->mem_table, 2 * qb + kb) != hipSuccess) throw Error(LGS_ERR_OOM, "hipMalloc failed for icp ref");
+    double2* tq = (double2*)ref->mem_table;
+    double2* tn = (double2*)((char*)ref->mem_table + qb);
+    int2* tkj = (int2*)((char*)ref->mem_table + 2 * qb);
+
+    // the table, the boxes
+    const size_t bb = icp_align256(sizeof(RefScanBox) * (size_t)K);
+    double bx[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
+    if (m > 0) {
+        scans_to_device(ctx, scans, K);
+        for (int k = 0; k < K; ++k) {
+            jobs[(size_t)k].ranges = scans[k]->d_ranges;
+            jobs[(size_t)k].angles = scans[k]->d_angles;
+        }
+        char* small = (char*)ctx->ensure(S_ICP0, bb + 256);
+        int* d_err = (int*)(small + bb);
+        LGS_HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
+        Upload up(ctx);
+        const size_t jo = up.append(jobs.data(), jobs.size());
+        up.flush();
+        hipLaunchKernelGGL(k_icpref_table, dim3(K), dim3(kIcpThreads), 0, ctx->stream, up.at<RefScanJob>(jo),
+                           p->max_segment_length * p->max_segment_length, tq, tn, tkj, (RefScanBox*)small, d_err);
+        LGS_HIP_CHECK(hipGetLastError());
+        char* pin = (char*)ctx->ensure_pinned(bb + 256);
+        LGS_HIP_CHECK(hipMemcpyAsync(pin, small, bb + 256, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        if (*(const int*)(pin + bb) != 0) throw Error(LGS_ERR_INTERNAL, kSincosMsg);
+        const RefScanBox* box = (const RefScanBox*)pin;
+        for (int k = 0; k < K; ++k) {
+            bx[0] = std::fmin(bx[0], box[k].min_x);
+            bx[1] = std::fmax(bx[1], box[k].max_x);
+            bx[2] = std::fmin(bx[2], box[k].min_y);
+            bx[3] = std::fmax(bx[3], box[k].max_y);
+            ref->lines += box[k].lines;
+        }
+    }
+
+    // the grid
+    const IcpRefGrid g = icp_ref_geometry(bx[0], bx[1], bx[2], bx[3], p->max_correspondence_dist);
+    const size_t ncell = (size_t)g.x.n * (size_t)g.y.n;
+    const size_t ib = icp_align256(sizeof(int) * mm), sb = icp_align256(sizeof(int) * (ncell + 1));
+    if (hipMalloc(&ref->mem_cells, qb + ib + sb) != hipSuccess) throw Error(LGS_ERR_OOM, "hipMalloc failed for icp ref");
+    double2* cq = (double2*)ref->mem_cells;
+    int* cidx = (int*)((char*)ref->mem_cells + qb);
+    int* starts = (int*)((char*)ref->mem_cells + qb + ib);
+    // (entries without a cell leave the tail of cq / cidx unused: defined bytes all the same)
+    LGS_HIP_CHECK(hipMemsetAsync(ref->mem_cells, 0, qb + ib + sb, ctx->stream));
+    if (m > 0) {
+        int* counts = (int*)ctx->ensure(S_ICPR0, sizeof(int) * ncell);
+        LGS_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int) * ncell, ctx->stream));
+        const int blocks = (m + 255) / 256;
+        hipLaunchKernelGGL(k_icpref_count, dim3(blocks), dim3(256), 0, ctx->stream, tq, m, g, counts);
+        LGS_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_icpref_scan, dim3(1), dim3(kIcpThreads), 0, ctx->stream, counts, (int)ncell, starts);
+        LGS_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_icpref_scatter, dim3(blocks), dim3(256), 0, ctx->stream, tq, m, g, starts, counts, cq, cidx);
+        LGS_HIP_CHECK(hipGetLastError());
+    }
+    ctx->sync();
+    ref->dev = IcpRefDev{ tq, tn, tkj, cq, cidx, starts, g, m };
+    return ref.release();
+}
+
+// the checks of a refine-time call that need no device (throw LGS_ERR_INVALID_ARG)
+void ref_call_check(const lgs_ctx* ctx, const lgs_icp_ref* ref, const lgs_scan* scan, lgs_pose2d pose,
+                    const lgs_icp_params* p)
+{
+    LGS_REQUIRE(ref && scan, "icp ref: null argument");
+    LGS_REQUIRE(ref->ctx == ctx, "icp ref: the reference belongs to another context");
+    LGS_REQUIRE(icp_ref_bound_same(ref->bound, p),
+                "icp ref: usable range, max_segment_length and max_correspondence_dist must be the reference's");
+    LGS_REQUIRE(scan->n >= 1, "icp ref: empty scan");
+    LGS_REQUIRE(icp_pose_finite(pose), "icp ref: pose not finite");
+}
+
+IcpItem ref_item_host(const lgs_scan* scan, lgs_pose2d sensor, const lgs_icp_params* p)
+{
+    LGS_REQUIRE(icp_pose_finite(sensor), "icp ref: pose not finite");
+    IcpItem it;
+    std::memset(&it, 0, sizeof(it));
+    it.spose[0] = sensor.x;
+    it.spose[1] = sensor.y;
+    it.spose[2] = sensor.theta;
+    it.slo = std::max(p->usable_range_min, scan->min_range);
+    it.shi = std::min(p->usable_range_max, scan->max_range);
+    it.sn = scan->n;
+    return it;
+}
+
+void run_icp_ref(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs_scan* const* scans, const lgs_pose2d* init,
+                 int n, const lgs_icp_params* p, lgs_icp_summary* out, double* traj)
+{
+    // every check before any device work
+    std::vector<IcpRefItem> items((size_t)n);
+    std::vector<lgs_pose2d> sensor((size_t)n);
+    for (int j = 0; j < n; ++j) {
+        ref_call_check(ctx, refs[j], scans[j], init[j], p);
+        sensor[(size_t)j] = compound(init[j], scans[j]->rel);
+        items[(size_t)j].it = ref_item_host(scans[j], sensor[(size_t)j], p);
+        items[(size_t)j].ref = refs[j]->dev;
+    }
+    LGS_HIP_CHECK(hipSetDevice(ctx->device));
+    scans_to_device(ctx, scans, n);
+    const int steps = std::max(1, p->num_iterations_max);
+    const size_t rb = icp_align256(sizeof(IcpRecord) * (size_t)n);
+    const size_t tb = traj ? icp_align256(sizeof(double) * 5 * (size_t)steps) : 0;
+    const size_t hb = rb + tb + 256;
+    char* small = (char*)ctx->ensure(S_ICP0, hb);
+    IcpRecord* d_rec = (IcpRecord*)small;
+    double* d_traj = traj ? (double*)(small + rb) : nullptr;
+    int* d_err = (int*)(small + rb + tb);
+    LGS_HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
+    for (int j = 0; j < n; ++j) {
+        IcpItem& it = items[(size_t)j].it;
+        it.s_ranges = scans[j]->d_ranges;
+        it.s_angles = scans[j]->d_angles;
+        it.traj = d_traj;   // lone calls only (n == 1)
+    }
+    Upload up(ctx);
+    const size_t io = up.append(items.data(), items.size());
+    up.flush();
+    const IcpShared sh = icp_shared(p);
+    for (int j0 = 0; j0 < n; j0 += kRefChunk) {
+        const int m = std::min(kRefChunk, n - j0);
+        hipLaunchKernelGGL(k_icp_ref, dim3(m), dim3(kIcpThreads), 0, ctx->stream, up.at<IcpRefItem>(io) + j0, sh,
+                           d_rec + j0, d_err);
+        LGS_HIP_CHECK(hipGetLastError());
+    }
+    char* pin = (char*)ctx->ensure_pinned(hb);
+    LGS_HIP_CHECK(hipMemcpyAsync(pin, small, hb, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    if (*(const int*)(pin + rb + tb) != 0) throw Error(LGS_ERR_INTERNAL, kSincosMsg);
+    const IcpRecord* rec = (const IcpRecord*)pin;
+    for (int j = 0; j < n; ++j)
+        icp_summary_of(rec[j], p, init[j], sensor[(size_t)j], scans[j]->rel, scans[j]->n, out[j]);
+    if (traj) std::memcpy(traj, pin + rb, sizeof(double) * 5 * (size_t)out[0].iterations);
+}
+
+}  // namespace
+
+extern "C" int lgs_icp_ref_create(lgs_ctx* ctx, const lgs_scan* const* ref_scans, const lgs_pose2d* ref_poses,
+                                  int n_refs, const lgs_icp_params* params, lgs_icp_ref** out)
+{
+    if (!ctx || !ref_scans || !ref_poses || !params || !out) return LGS_ERR_INVALID_ARG;
+    if (icp_params_check(params) != LGS_OK) return LGS_ERR_INVALID_ARG;
+    return guarded(ctx, [&] { *out = ref_create(ctx, ref_scans, ref_poses, n_refs, params); });
+}
+
+extern "C" void lgs_icp_ref_destroy(lgs_icp_ref* ref) { icp_ref_free(ref); }
+
+extern "C" int lgs_icp_ref_info(const lgs_icp_ref* ref, int* n_refs, int* entries, int* lines, int* cells_x,
+                                int* cells_y, double* cell_size)
+{
+    if (!ref) return LGS_ERR_INVALID_ARG;
+    if (n_refs) *n_refs = ref->n_refs;
+    if (entries) *entries = ref->entries;
+    if (lines) *lines = ref->lines;
+    if (cells_x) *cells_x = ref->dev.g.x.n;
+    if (cells_y) *cells_y = ref->dev.g.y.n;
+    if (cell_size) *cell_size = ref->dev.g.c;
+    return LGS_OK;
+}
+
+extern "C" int lgs_icp_ref_optimize_pose_batch(lgs_ctx* ctx, const lgs_icp_ref* const* refs,
+                                               const lgs_scan* const* scans, const lgs_pose2d* initial_poses, int n,
+                                               const lgs_icp_params* params, lgs_icp_summary* out)
+{
+    if (!ctx || !refs || !scans || !initial_poses || !params || !out || n < 0) return LGS_ERR_INVALID_ARG;
+    if (icp_params_check(params) != LGS_OK) return LGS_ERR_INVALID_ARG;
+    if (n == 0) return LGS_OK;
+    return guarded(ctx, [&] {
+        // a failing call writes nothing: the summaries are formed aside
+        std::vector<lgs_icp_summary> tmp((size_t)n);
+        run_icp_ref(ctx, refs, scans, initial_poses, n, params, tmp.data(), nullptr);
+        std::memcpy(out, tmp.data(), sizeof(lgs_icp_summary) * (size_t)n);
+    });
+}
+
+extern "C" int lgs_icp_ref_optimize_pose(lgs_ctx* ctx, const lgs_icp_ref* ref, const lgs_scan* scan,
+                                         lgs_pose2d initial_pose, const lgs_icp_params* params, lgs_icp_summary* out,
+                                         double* trajectory)
+{
+    if (!ctx || !ref || !scan || !params || !out) return LGS_ERR_INVALID_ARG;
+    if (icp_params_check(params) != LGS_OK) return LGS_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        lgs_icp_summary tmp;
+        std::vector<double> tr(trajectory ? 5 * (size_t)std::max(1, params->num_iterations_max) : 0);
+        run_icp_ref(ctx, &ref, &scan, &initial_pose, 1, params, &tmp, trajectory ? tr.data() : nullptr);
+        if (trajectory) std::memcpy(trajectory, tr.data(), sizeof(double) * 5 * (size_t)tmp.iterations);
+        *out = tmp;
+    });
+}
+
+extern "C" int lgs_icp_ref_pairs(lgs_ctx* ctx, const lgs_icp_ref* ref, const lgs_scan* scan, lgs_pose2d sensor_pose,
+                                 const lgs_icp_params* params, int* ref_index, int* beam_index, double* residual)
+{
+    if (!ctx || !ref || !scan || !params || !ref_index || !beam_index || !residual) return LGS_ERR_INVALID_ARG;
+    if (icp_params_check(params) != LGS_OK) return LGS_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        ref_call_check(ctx, ref, scan, sensor_pose, params);
+        IcpRefItem X;
+        X.it = ref_item_host(scan, sensor_pose, params);
+        X.ref = ref->dev;
+        LGS_HIP_CHECK(hipSetDevice(ctx->device));
+        scans_to_device(ctx, &scan, 1);
+        X.it.s_ranges = scan->d_ranges;
+        X.it.s_angles = scan->d_angles;
+        const size_t ib = icp_align256(sizeof(int) * (size_t)scan->n), eb = icp_align256(sizeof(double) * (size_t)scan->n);
+        const size_t hb = eb + 2 * ib + 256;
+        char* d = (char*)ctx->ensure(S_ICP1, hb);
+        int* d_err = (int*)(d + eb + 2 * ib);
+        LGS_HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
+        hipLaunchKernelGGL(k_icp_ref_pairs, dim3(1), dim3(kIcpThreads), 0, ctx->stream, X, icp_shared(params),
+                           (int*)(d + eb), (int*)(d + eb + ib), (double*)d, d_err);
+        LGS_HIP_CHECK(hipGetLastError());
+        char* pin = (char*)ctx->ensure_pinned(hb);
+        LGS_HIP_CHECK(hipMemcpyAsync(pin, d, hb, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        if (*(const int*)(pin + eb + 2 * ib) != 0) throw Error(LGS_ERR_INTERNAL, kSincosMsg);
+        std::memcpy(residual, pin, sizeof(double) * (size_t)scan->n);
+        std::memcpy(ref_index, pin + eb, sizeof(int) * (size_t)scan->n);
+        std::memcpy(beam_index, pin + eb + ib, sizeof(int) * (size_t)scan->n);
+    });
+}

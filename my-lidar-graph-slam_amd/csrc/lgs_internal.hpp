@@ -92,6 +92,7 @@ enum Slot {
     S_PG0, S_PG1,   // pose-graph CG (k_pgcg.hip): the block pattern; values, right-hand side, vectors, result
     S_PG2, S_PG3,   // resident pose-graph LM (k_pglm.hip): incidence lists and edges; poses, loss terms, step record
     S_ICP0, S_ICP1, // point-to-line ICP (k_icp.hip): records, trajectory, error word; lgs_icp_pairs' outputs
+    S_ICPR0,        // lgs_icp_ref_create (k_icp_ref.hip): per-scan boxes and the cell counts of a build
     // bank 1 of the per-batch buffers: a batched call keeps two 64-query
     // chunks in flight (the next chunk's launches go out before the host
     // finishes the previous one), each in its own bank (lgs_ctx::banked)

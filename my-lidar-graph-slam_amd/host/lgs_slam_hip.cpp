@@ -470,6 +470,33 @@ void ScanMatcherIcpPointToLineHip::SetReference(ScanDataPtr refScan, const Robot
 {
     mRefScan = std::move(refScan);
     mRefPose = refPose;
+    if (mRef) lgs_icp_ref_destroy(mRef);
+    mRef = nullptr;
+}
+
+void ScanMatcherIcpPointToLineHip::SetReference(const std::vector<ScanDataPtr>& refScans,
+                                                const std::vector<RobotPose2D<double>>& refPoses)
+{
+    if (refScans.empty() || refScans.size() != refPoses.size())
+        throw Error(LGS_ERR_INVALID_ARG, "ScanMatcherIcpPointToLineHip: need as many reference poses as scans, at least one");
+    std::vector<const lgs_scan*> scans;
+    std::vector<lgs_pose2d> poses;
+    for (std::size_t k = 0; k < refScans.size(); ++k) {
+        if (!refScans[k]) throw Error(LGS_ERR_INVALID_ARG, "ScanMatcherIcpPointToLineHip: null scan");
+        scans.push_back(refScans[k]->Handle());
+        poses.push_back(to_c(refPoses[k]));
+    }
+    lgs_icp_ref* ref = nullptr;
+    mDev->Check(lgs_icp_ref_create(mDev->Handle(), scans.data(), poses.data(), (int)scans.size(), &mParams, &ref),
+                "lgs_icp_ref_create");
+    if (mRef) lgs_icp_ref_destroy(mRef);
+    mRef = ref;
+    mRefScan.reset();
+}
+
+ScanMatcherIcpPointToLineHip::~ScanMatcherIcpPointToLineHip()
+{
+    if (mRef) lgs_icp_ref_destroy(mRef);
 }
 
 ScanMatchingSummary ScanMatcherIcpPointToLineHip::OptimizePose(const ScanDataPtr& refScan,
@@ -492,6 +519,19 @@ ScanMatchingSummary ScanMatcherIcpPointToLineHip::OptimizePose(const ScanDataPtr
 
 ScanMatchingSummary ScanMatcherIcpPointToLineHip::OptimizePose(const ScanMatchingQuery& q)
 {
+    if (mRef) {
+        if (!q.mScanData) throw Error(LGS_ERR_INVALID_ARG, "ScanMatcherIcpPointToLineHip: null scan");
+        mDev->Check(lgs_icp_ref_optimize_pose(mDev->Handle(), mRef, q.mScanData->Handle(), to_c(q.mInitialPose), &mParams,
+                                              &mLast, nullptr),
+                    "lgs_icp_ref_optimize_pose");
+        ScanMatchingSummary o;
+        o.mPoseFound = mLast.pose_found != 0;
+        o.mNormalizedCost = mLast.normalized_cost;
+        o.mInitialPose = from_c(mLast.initial_pose);
+        o.mEstimatedPose = from_c(mLast.estimated_pose);
+        o.mEstimatedCovariance = cov_of(mLast.covariance);
+        return o;
+    }
     if (!mRefScan) throw Error(LGS_ERR_INVALID_ARG, "ScanMatcherIcpPointToLineHip: no reference scan set");
     return OptimizePose(mRefScan, mRefPose, q.mScanData, q.mInitialPose);
 }

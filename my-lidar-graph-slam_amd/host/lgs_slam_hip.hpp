@@ -402,6 +402,13 @@ public:
     ScanMatcherIcpPointToLineHip(DevicePtr dev, const IcpPointToLineParams& params);
     // the scan later queries are matched against, and its robot pose
     void SetReference(ScanDataPtr refScan, const RobotPose2D<double>& refPose);
+    // a set of scans at their robot poses as the reference (lgs_icp_ref_*,
+    // DESIGN.md §4.5c): the table is built here, once, and the scans are not
+    // kept; later queries run against it.  Replaces any earlier reference
+    void SetReference(const std::vector<ScanDataPtr>& refScans, const std::vector<RobotPose2D<double>>& refPoses);
+    ~ScanMatcherIcpPointToLineHip() override;
+    ScanMatcherIcpPointToLineHip(const ScanMatcherIcpPointToLineHip&) = delete;
+    ScanMatcherIcpPointToLineHip& operator=(const ScanMatcherIcpPointToLineHip&) = delete;
     ScanMatchingSummary OptimizePose(const ScanDataPtr& refScan, const RobotPose2D<double>& refPose,
                                      const ScanDataPtr& scan, const RobotPose2D<double>& initialPose);
     // the query's scan against the reference (the query's grid map is not
@@ -415,6 +422,7 @@ private:
     lgs_icp_params mParams{};
     ScanDataPtr mRefScan;
     RobotPose2D<double> mRefPose;
+    lgs_icp_ref* mRef = nullptr;   // the multi-scan reference, when that was set last
     lgs_icp_summary mLast{};
 };
 

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from typing import Optional, Sequence
 
 import numpy as np
@@ -456,6 +457,17 @@ _PROTOS = [
                                               C.c_int, C.POINTER(IcpParams), C.POINTER(IcpSummary)]),
     ("lgs_icp_pairs", C.c_int, [_P, _P, Pose2D, _P, Pose2D, C.POINTER(IcpParams), C.POINTER(C.c_int),
                                 C.POINTER(C.c_double)]),
+    ("lgs_icp_ref_create", C.c_int, [_P, C.POINTER(_P), C.POINTER(Pose2D), C.c_int, C.POINTER(IcpParams),
+                                     C.POINTER(_P)]),
+    ("lgs_icp_ref_destroy", None, [_P]),
+    ("lgs_icp_ref_info", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("lgs_icp_ref_optimize_pose", C.c_int, [_P, _P, _P, Pose2D, C.POINTER(IcpParams), C.POINTER(IcpSummary),
+                                            C.POINTER(C.c_double)]),
+    ("lgs_icp_ref_optimize_pose_batch", C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(Pose2D), C.c_int,
+                                                  C.POINTER(IcpParams), C.POINTER(IcpSummary)]),
+    ("lgs_icp_ref_pairs", C.c_int, [_P, _P, _P, Pose2D, C.POINTER(IcpParams), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_double)]),
     ("lgs_debug_keysort", C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
     ("lgs_debug_map_rebuilds", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("lgs_debug_copy_counters", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -981,6 +993,16 @@ class Context:
                    "icp_pairs")
         return index, residual
 
+    def icp_ref(self, scans, poses, params: "IcpParams") -> "IcpRef":
+        """lgs_icp_ref_create: a set of reference scans at robot poses as one
+        table behind a grid; the scans may be closed afterwards."""
+        n = len(scans)
+        arr = (_P * max(1, n))(*[s.h for s in scans])
+        ps = (Pose2D * max(1, n))(*[Pose2D(*p) for p in poses])
+        h = _P()
+        self.check(self.lib.lgs_icp_ref_create(self.h, arr, ps, n, C.byref(params), C.byref(h)), "icp_ref_create")
+        return IcpRef(self, h)
+
     def cost_square_error(self, grid, umin: float, umax: float, scan, sensor_pose, covariance: bool = False):
         v = C.c_double()
         cov = (C.c_double * 9)() if covariance else None
@@ -1374,6 +1396,67 @@ class Map:
     def close(self):
         if self.h:
             self.ctx.lib.lgs_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IcpRef:
+    """lgs_icp_ref: the reference of the multi-scan point-to-line ICP."""
+    RefInfo = namedtuple("RefInfo", "n_refs entries lines cells_x cells_y cell_size")
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def info(self):
+        v = [C.c_int() for _ in range(5)]
+        c = C.c_double()
+        self.ctx.check(self.ctx.lib.lgs_icp_ref_info(self.h, *[C.byref(x) for x in v], C.byref(c)), "icp_ref_info")
+        return IcpRef.RefInfo(*[x.value for x in v], c.value)
+
+    def refine(self, scan, init, params: "IcpParams", trajectory: bool = False):
+        """lgs_icp_ref_optimize_pose; as Context.icp"""
+        out = IcpSummary()
+        traj = np.zeros(5 * max(1, params.num_iterations_max)) if trajectory else None
+        self.ctx.check(self.ctx.lib.lgs_icp_ref_optimize_pose(self.ctx.h, self.h, scan.h, Pose2D(*init), C.byref(params),
+                                                              C.byref(out), dptr(traj) if trajectory else None),
+                       "icp_ref_optimize_pose")
+        if trajectory:
+            return out, [tuple(traj[5 * k: 5 * k + 5]) for k in range(out.iterations)]
+        return out
+
+    def refine_batch(self, scans, inits, params: "IcpParams", refs=None):
+        """lgs_icp_ref_optimize_pose_batch: item j is scans[j] from inits[j]
+        against refs[j] (default: this reference for every item)"""
+        n = len(scans)
+        ctx = self.ctx
+        refs = [self] * n if refs is None else refs
+        rarr = (_P * max(1, n))(*[r.h for r in refs])
+        sarr = (_P * max(1, n))(*[s.h for s in scans])
+        poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in inits])
+        out = (IcpSummary * max(1, n))()
+        ctx.check(ctx.lib.lgs_icp_ref_optimize_pose_batch(ctx.h, rarr, sarr, poses, n, C.byref(params), out),
+                  "icp_ref_optimize_pose_batch")
+        return list(out)[:n]
+
+    def pairs(self, scan, sensor_pose, params: "IcpParams"):
+        """lgs_icp_ref_pairs: (reference scan, its beam, residual) per beam of `scan`"""
+        n = len(scan.ranges)
+        k, j = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        residual = np.zeros(n)
+        ip = C.POINTER(C.c_int)
+        self.ctx.check(self.ctx.lib.lgs_icp_ref_pairs(self.ctx.h, self.h, scan.h, Pose2D(*sensor_pose), C.byref(params),
+                                                      k.ctypes.data_as(ip), j.ctypes.data_as(ip), dptr(residual)),
+                       "icp_ref_pairs")
+        return k, j, residual
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lgs_icp_ref_destroy(self.h)
             self.h = None
 
     def __del__(self):

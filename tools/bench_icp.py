@@ -8,6 +8,9 @@ Prints one JSON line per measurement:
   lone    lgs_icp_optimize_pose: p50 / p90 of the call (the host clock around
           a call that ends in a synchronisation), steps and pairs
   batch   lgs_icp_optimize_pose_batch of 256 refines: refines/s, time per refine
+  ref_lone, ref_batch   the same refines through lgs_icp_ref_* against a
+          reference of --ref-scans K scans: lgs_icp_ref_create's
+          time, the lone refine, the batch of 256 (K = 1: the bytes of `lone`)
   k4      lgs_linsolve_optimize_pose (lone p50 / p90) and _batch of 256
 
 The GPU measurements run in one child process under a time limit; a child that
@@ -82,6 +85,70 @@ def gpu_step(args):
     print(json.dumps(dict(line="batch", matcher="icp", refines=BATCH, beams=len(ang), call_ms=round(1e3 * wall, 3),
                           refines_per_s=round(BATCH / wall, 1), us_per_refine=round(1e6 * wall / BATCH, 2),
                           found=int(sum(o.pose_found for o in out)))), flush=True)
+    # the same refines against a reference of K scans behind a grid (lgs_icp_ref_*):
+    # item k's reference scan plus K - 1 scans taken a few centimetres further on; with K = 1 the
+    # bytes are lgs_icp_optimize_pose's above
+    K, nref = args.ref_scans, min(args.lone, BATCH)
+    sets = []
+    for k in range(nref):
+        rp = [(ref_poses[k][0] + 0.04 * i, ref_poses[k][1] - 0.03 * i, ref_poses[k][2] + 0.01 * i) for i in range(K)]
+        sets.append(([refs[k]] + [ctx.scan(scene.ray_cast(world, p, ang), ang) for p in rp[1:]], rp))
+    create = []
+    handles = []
+    for k in range(-args.warmup, nref):
+        t0 = time.perf_counter()
+        h = ctx.icp_ref(*sets[max(k, 0)], P)
+        if k >= 0:
+            create.append(time.perf_counter() - t0)
+            handles.append(h)
+    info = handles[0].info()
+    for k in range(args.warmup):
+        handles[k % nref].refine(scans[k % nref], inits[k % nref], P)
+    lone_r, outs_r = [], []
+    for k in range(nref):
+        t0 = time.perf_counter()
+        o = handles[k].refine(scans[k], inits[k], P)
+        lone_r.append(time.perf_counter() - t0)
+        outs_r.append(o)
+    err = [float(np.hypot(o.estimated_pose.x - items[k][1][0], o.estimated_pose.y - items[k][1][1]))
+           for k, o in enumerate(outs_r)]
+    # the items differ in how many entries a beam looks at; the spread of one item's repeated calls
+    again = []
+    for _ in range(8):
+        t0 = time.perf_counter()
+        handles[0].refine(scans[0], inits[0], P)
+        again.append(time.perf_counter() - t0)
+    print(json.dumps(dict(line="ref_lone", matcher="icp_ref", ref_scans=K, calls=len(lone_r), beams=len(ang),
+                          entries=info.entries, cells=[info.cells_x, info.cells_y], cell_size=info.cell_size,
+                          create_p50_us=pct(create, 50), create_p90_us=pct(create, 90),
+                          p50_us=pct(lone_r, 50), p90_us=pct(lone_r, 90), p10_us=pct(lone_r, 10),
+                          item0_repeated_us=[pct(again, 0), pct(again, 50), pct(again, 100)],
+                          steps_mean=round(float(np.mean([o.iterations for o in outs_r])), 2),
+                          pairs_mean=round(float(np.mean([o.num_pairs for o in outs_r])), 1),
+                          found=int(sum(o.pose_found for o in outs_r)),
+                          p50_us_per_pass=round(pct(lone_r, 50) / (ICP[0] + 1), 2),
+                          median_error_m=float(np.median(err)),
+                          equals_icp_bytes=(all(bytes(a) == bytes(b) for a, b in zip(outs_r, outs)) if K == 1 else None))),
+          flush=True)
+    # the batch of 256 cycles through the nref references made above
+    b_refs = [handles[j % nref] for j in range(BATCH)]
+    b_scans, b_inits = [scans[j % nref] for j in range(BATCH)], [inits[j % nref] for j in range(BATCH)]
+    call = lambda: handles[0].refine_batch(b_scans, b_inits, P, refs=b_refs)
+    for _ in range(args.warmup):
+        call()
+    t = []
+    for _ in range(args.steps):
+        t0 = time.perf_counter()
+        out = call()
+        t.append(time.perf_counter() - t0)
+    wall = float(np.median(t))
+    print(json.dumps(dict(line="ref_batch", matcher="icp_ref", ref_scans=K, refines=BATCH, distinct_refs=nref,
+                          beams=len(ang), call_ms=round(1e3 * wall, 3), call_ms_min=round(1e3 * min(t), 3),
+                          call_ms_max=round(1e3 * max(t), 3), refines_per_s=round(BATCH / wall, 1),
+                          us_per_refine=round(1e6 * wall / BATCH, 2), found=int(sum(o.pose_found for o in out)))),
+          flush=True)
+    for h in handles:
+        h.close()
     # K4 on a map of the same scene, the same current scans and starts
     m = ob.OMap(0.05, 100, 300, 300)
     bp = ob.BuilderParams(0.01, 20.0, 0.6, 0.45)
@@ -119,6 +186,7 @@ def main():
     ap.add_argument("--lone", type=int, default=32, help="lone calls timed")
     ap.add_argument("--steps", type=int, default=5, help="timed batch calls")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--ref-scans", type=int, default=1, help="reference scans per lgs_icp_ref (the ref path)")
     ap.add_argument("--timeout", type=float, default=240.0, help="time limit of the GPU step (s)")
     ap.add_argument("--step", choices=["gpu"], help=argparse.SUPPRESS)   # child mode
     args = ap.parse_args()
@@ -126,7 +194,7 @@ def main():
         gpu_step(args)
         return 0
     cmd = [sys.executable, os.path.abspath(__file__), "--step", "gpu", "--beams", str(args.beams), "--lone",
-           str(args.lone), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+           str(args.lone), "--steps", str(args.steps), "--warmup", str(args.warmup), "--ref-scans", str(args.ref_scans)]
     try:
         rc = subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
