@@ -27,6 +27,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_icp
 	$(MAKE) -C tests/cpp_icp_ref
 	$(MAKE) -C tests/cpp_hv
+	$(MAKE) -C tests/cpp_loop
 
 clean:
 	$(MAKE) -C my-lidar-graph-slam_amd/csrc clean
@@ -44,5 +45,6 @@ clean:
 	$(MAKE) -C tests/cpp_icp clean
 	$(MAKE) -C tests/cpp_icp_ref clean
 	$(MAKE) -C tests/cpp_hv clean
+	$(MAKE) -C tests/cpp_loop clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean

@@ -34,6 +34,7 @@
 //                the first descent), wave-aggregated appends
 //   k_bb_rescore exact re-score of a node from host (glibc) cells
 #include "lgs_internal.hpp"
+#include "loop_host.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -1032,12 +1033,9 @@ extern "C" int lgs_bb_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* gri
     if (const int rc = cost_select(cost, &sel)) return rc;
     if (!sel.alt) return lgs_bb_optimize_pose_batch(ctx, grid, pyramid, params, sel.ge, scans, initial, n, nthr, out);
     if (!out || n < 0) return LGS_ERR_INVALID_ARG;
-    std::vector<lgs_rtcsm_summary> tmp;
-    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)n); });
-    if (rc0 != LGS_OK) return rc0;
-    const int rc = bb_batch_run(ctx, grid, pyramid, params, sel.ge, sel.alt, scans, initial, n, nthr, tmp.data());
-    if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(lgs_rtcsm_summary) * (size_t)n);
-    return rc;
+    return with_own_output(ctx, out, n, [&](lgs_rtcsm_summary* o) {
+        return bb_batch_run(ctx, grid, pyramid, params, sel.ge, sel.alt, scans, initial, n, nthr, o);
+    });
 }
 
 static int bb_query_run(lgs_ctx* ctx, const lgs_grid* grid, const lgs_bb_params* params,
@@ -1071,10 +1069,9 @@ extern "C" int lgs_bb_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* gri
     if (const int rc = cost_select(cost, &sel)) return rc;
     if (!sel.alt) return lgs_bb_optimize_pose_query(ctx, grid, params, sel.ge, scan, initial, out);
     if (!out) return LGS_ERR_INVALID_ARG;
-    lgs_rtcsm_summary tmp;
-    const int rc = bb_query_run(ctx, grid, params, sel.ge, sel.alt, scan, initial, &tmp);
-    if (rc == LGS_OK) *out = tmp;
-    return rc;
+    return with_own_output(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
+        return bb_query_run(ctx, grid, params, sel.ge, sel.alt, scan, initial, o);
+    });
 }
 
 static int loop_detect_bb_run(lgs_ctx* ctx, const lgs_bb_params* params, const lgs_cost_ge_params* cost,
@@ -1087,21 +1084,12 @@ static int loop_detect_bb_run(lgs_ctx* ctx, const lgs_bb_params* params, const l
         return LGS_ERR_INVALID_ARG;
     return guarded(ctx, [&] {
         check_bb(params, cost);
-        LGS_REQUIRE(score_threshold > 0.0 && score_threshold <= 1.0, "score threshold must be in (0, 1] (:18-19)");
-        int covered = 0;
-        for (int q = 0; q < num_queries; ++q) {
-            const lgs_loop_query& Q = queries[q];
-            LGS_REQUIRE(Q.map, "loop query without a local map");
-            LGS_REQUIRE(!alt || (long long)Q.map->w * Q.map->h < (1LL << 30),
+        const std::vector<int> query_of =
+            check_loop_batch(score_threshold, queries, num_queries, candidates, num_candidates, ":18-19");
+        // this matcher's own rule: with a square-error or exact cost, maps of fewer than 2^30 cells
+        for (int q = 0; q < num_queries; ++q)
+            LGS_REQUIRE(!alt || (long long)queries[q].map->w * queries[q].map->h < (1LL << 30),
                         "square-error or exact cost: map of 2^30 cells or more");
-            LGS_REQUIRE(Q.first_candidate == covered && Q.num_candidates >= 0 &&
-                            Q.first_candidate + Q.num_candidates <= num_candidates,
-                        "loop queries must cover the candidates contiguously and in order");
-            covered += Q.num_candidates;
-            for (int j = 0; j < Q.num_candidates; ++j)
-                LGS_REQUIRE(candidates[Q.first_candidate + j].scan, "loop candidate without a scan");
-        }
-        LGS_REQUIRE(covered == num_candidates, "loop queries must cover every candidate");
         // batches of whole queries, at most ~kBBBatch candidates: each query's
         // pyramid once per batch (LocalMapInfo caches it, :45-55)
         for (int q0 = 0; q0 < num_queries;) {
@@ -1115,7 +1103,7 @@ static int loop_detect_bb_run(lgs_ctx* ctx, const lgs_bb_params* params, const l
             std::vector<const double* const*> pp;
             std::vector<lgs_scan*> sc;
             std::vector<lgs_pose2d> poses;
-            std::vector<int> cand, qof;
+            std::vector<int> cand;
             for (int q = q0; q < q1; ++q)
                 for (int j = 0; j < queries[q].num_candidates; ++j) {
                     const lgs_loop_candidate& c = candidates[queries[q].first_candidate + j];
@@ -1124,27 +1112,13 @@ static int loop_detect_bb_run(lgs_ctx* ctx, const lgs_bb_params* params, const l
                     sc.push_back(const_cast<lgs_scan*>(c.scan));
                     poses.push_back(c.node_pose);
                     cand.push_back(queries[q].first_candidate + j);
-                    qof.push_back(q);
                 }
             std::vector<lgs_rtcsm_summary> sums(cand.size());
             if (!cand.empty())
                 run_bb(ctx, params, cost, grids.data(), pp.data(), sc.data(), poses.data(), (int)cand.size(),
                        score_threshold, sums.data(), false, alt);
-            for (size_t k = 0; k < cand.size(); ++k) {
-                const lgs_loop_query& Q = queries[qof[k]];
-                lgs_loop_result& r = results[cand[k]];
-                std::memset(&r, 0, sizeof(r));
-                const lgs_rtcsm_summary& s = sums[k];
-                r.found = s.pose_found;   // FindCorrespondingPose (:99-117)
-                r.start_node_index = Q.local_map_node_index;
-                r.end_node_index = candidates[cand[k]].node_index;
-                r.start_node_pose = Q.local_map_node_pose;
-                r.estimated_pose = s.estimated_pose;
-                r.score = s.score_max;
-                r.normalized_cost = s.normalized_cost;
-                if (s.pose_found) r.relative_pose = inverse_compound(Q.local_map_node_pose, s.estimated_pose);
-                std::memcpy(r.covariance, s.covariance, sizeof(r.covariance));
-            }
+            for (size_t k = 0; k < cand.size(); ++k)   // FindCorrespondingPose (:99-117)
+                fill_loop_result(results[cand[k]], queries[query_of[(size_t)cand[k]]], candidates[cand[k]], sums[k]);
             q0 = q1;
         }
     });
@@ -1171,11 +1145,8 @@ extern "C" int lgs_loop_detect_bb_cost(lgs_ctx* ctx, const lgs_bb_params* params
         return lgs_loop_detect_bb(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
                                   num_candidates, results);
     if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
-    std::vector<lgs_loop_result> tmp;
-    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
-    if (rc0 != LGS_OK) return rc0;
-    const int rc = loop_detect_bb_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries, candidates,
-                                      num_candidates, tmp.data());
-    if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
-    return rc;
+    return with_own_output(ctx, results, num_candidates, [&](lgs_loop_result* o) {
+        return loop_detect_bb_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries, candidates,
+                                  num_candidates, o);
+    });
 }

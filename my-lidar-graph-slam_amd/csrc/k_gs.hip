@@ -34,6 +34,7 @@
 // The greedy-endpoint cost and covariance at the best pose come from k_cost
 // (k_rtcsm.hip cost_summaries), the summary's pose algebra from host glibc.
 #include "lgs_internal.hpp"
+#include "loop_host.hpp"
 #include "glibc_math.hpp"
 
 #include <algorithm>
@@ -583,12 +584,9 @@ extern "C" int lgs_gs_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* gri
     if (const int rc = cost_select(cost, &sel)) return rc;
     if (!sel.alt) return lgs_gs_optimize_pose_batch(ctx, grid, params, sel.ge, scans, initial, n, nthr, out);
     if (n < 0 || (n > 0 && !out)) return LGS_ERR_INVALID_ARG;
-    std::vector<lgs_rtcsm_summary> tmp;
-    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)n); });
-    if (rc0 != LGS_OK) return rc0;
-    const int rc = gs_batch_run(ctx, grid, params, sel.ge, sel.alt, scans, initial, n, nthr, tmp.data());
-    if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(lgs_rtcsm_summary) * (size_t)n);
-    return rc;
+    return with_own_output(ctx, out, n, [&](lgs_rtcsm_summary* o) {
+        return gs_batch_run(ctx, grid, params, sel.ge, sel.alt, scans, initial, n, nthr, o);
+    });
 }
 
 extern "C" int lgs_gs_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_gs_params* params,
@@ -633,48 +631,25 @@ static int loop_detect_gs_run(lgs_ctx* ctx, const lgs_gs_params* params, const l
     return guarded(ctx, [&] {
         GSWindow win;
         check_gs(params, cost, win);
-        LGS_REQUIRE(score_threshold > 0.0 && score_threshold <= 1.0, "score threshold must be in (0, 1] (:20-21)");
-        int covered = 0;
+        const std::vector<int> query_of =
+            check_loop_batch(score_threshold, queries, num_queries, candidates, num_candidates, ":20-21");
         std::vector<const lgs_grid*> grids;
         std::vector<lgs_scan*> sc;
         std::vector<lgs_pose2d> poses;
-        std::vector<int> qof;
-        for (int q = 0; q < num_queries; ++q) {
-            const lgs_loop_query& Q = queries[q];
-            LGS_REQUIRE(Q.map, "loop query without a local map");
-            LGS_REQUIRE(Q.first_candidate == covered && Q.num_candidates >= 0 &&
-                            Q.first_candidate + Q.num_candidates <= num_candidates,
-                        "loop queries must cover the candidates contiguously and in order");
-            covered += Q.num_candidates;
-            for (int j = 0; j < Q.num_candidates; ++j) {
-                const lgs_loop_candidate& c = candidates[Q.first_candidate + j];
-                LGS_REQUIRE(c.scan && c.scan->n >= 1, "loop candidate without a scan");
-                grids.push_back(Q.map);   // the candidates of one query share its map
-                sc.push_back(const_cast<lgs_scan*>(c.scan));
-                poses.push_back(c.node_pose);
-                qof.push_back(q);
-            }
+        for (int k = 0; k < num_candidates; ++k) {
+            const lgs_loop_candidate& c = candidates[k];
+            // this matcher's own rule (no scan can be created empty; run_gs relies on it)
+            LGS_REQUIRE(c.scan->n >= 1, "empty scan");
+            grids.push_back(queries[query_of[(size_t)k]].map);   // the candidates of one query share its map
+            sc.push_back(const_cast<lgs_scan*>(c.scan));
+            poses.push_back(c.node_pose);
         }
-        LGS_REQUIRE(covered == num_candidates, "loop queries must cover every candidate");
         if (num_candidates == 0) return;
         std::vector<lgs_rtcsm_summary> sums((size_t)num_candidates);
         run_gs(ctx, params, cost, win, grids.data(), sc.data(), poses.data(), num_candidates, score_threshold,
                sums.data(), nullptr, alt);
-        for (int k = 0; k < num_candidates; ++k) {
-            const lgs_loop_query& Q = queries[qof[(size_t)k]];
-            const lgs_rtcsm_summary& s = sums[(size_t)k];
-            lgs_loop_result& r = results[k];
-            std::memset(&r, 0, sizeof(r));
-            r.found = s.pose_found;   // FindCorrespondingPose (:88-106)
-            r.start_node_index = Q.local_map_node_index;
-            r.end_node_index = candidates[k].node_index;
-            r.start_node_pose = Q.local_map_node_pose;
-            r.estimated_pose = s.estimated_pose;
-            r.score = s.score_max;
-            r.normalized_cost = s.normalized_cost;
-            if (s.pose_found) r.relative_pose = inverse_compound(Q.local_map_node_pose, s.estimated_pose);
-            std::memcpy(r.covariance, s.covariance, sizeof(r.covariance));
-        }
+        for (int k = 0; k < num_candidates; ++k)   // FindCorrespondingPose (:88-106)
+            fill_loop_result(results[k], queries[query_of[(size_t)k]], candidates[k], sums[(size_t)k]);
     });
 }
 
@@ -699,11 +674,8 @@ extern "C" int lgs_loop_detect_gs_cost(lgs_ctx* ctx, const lgs_gs_params* params
         return lgs_loop_detect_gs(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
                                   num_candidates, results);
     if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
-    std::vector<lgs_loop_result> tmp;
-    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
-    if (rc0 != LGS_OK) return rc0;
-    const int rc = loop_detect_gs_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries, candidates,
-                                      num_candidates, tmp.data());
-    if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
-    return rc;
+    return with_own_output(ctx, results, num_candidates, [&](lgs_loop_result* o) {
+        return loop_detect_gs_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries, candidates,
+                                  num_candidates, o);
+    });
 }

@@ -34,6 +34,7 @@
 //               seven costs bit for bit (ge_cost_device.hpp: restated sincos,
 //               table terms, beam-order sums; no guards, no host fix-up).
 #include "lgs_internal.hpp"
+#include "loop_host.hpp"
 #include "fast_cell.hpp"
 #include "hv_zero.hpp"
 #include "sq_cost_stage.hpp"
@@ -6196,17 +6197,6 @@ void check_alt_maps(const CostAlt& alt, const lgs_grid* const* grids, int n)
                     "exact cost: map resolution finite and > 0");
     }
 }
-template <class F>
-int with_own_summaries(lgs_ctx* ctx, lgs_rtcsm_summary* out, int n, F&& f)
-{
-    std::vector<lgs_rtcsm_summary> tmp;
-    const int rc = guarded(ctx, [&] {
-        tmp.resize((size_t)n);
-        f(tmp.data());
-    });
-    if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(lgs_rtcsm_summary) * (size_t)n);
-    return rc;
-}
 }  // namespace
 
 extern "C" int lgs_rtcsm_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* grid, const lgs_grid* coarse,
@@ -6219,7 +6209,7 @@ extern "C" int lgs_rtcsm_optimize_pose_batch_cost(lgs_ctx* ctx, const lgs_grid* 
     if (!sel.alt) return lgs_rtcsm_optimize_pose_batch(ctx, grid, coarse, params, sel.ge, scans, initial, n, nthr, out);
     if (!ctx || !out || !scans || !initial || n < 0 || !grid || !coarse) return LGS_ERR_INVALID_ARG;
     if (n == 0) return LGS_OK;
-    return with_own_summaries(ctx, out, n, [&](lgs_rtcsm_summary* o) {
+    return with_own_output(ctx, out, n, [&](lgs_rtcsm_summary* o) {
         check_alt_maps(sel.alt, &grid, 1);
         std::vector<PlaneSet> sets(1);
         sets[0].coarse = coarse;
@@ -6239,7 +6229,7 @@ extern "C" int lgs_rtcsm_optimize_pose_cost(lgs_ctx* ctx, const lgs_grid* grid, 
     if (const int rc = cost_select(cost, &sel)) return rc;
     if (!sel.alt) return lgs_rtcsm_optimize_pose(ctx, grid, coarse, params, sel.ge, scan, initial, nthr, out);
     if (!ctx || !out || !grid || !coarse || !scan) return LGS_ERR_INVALID_ARG;
-    return with_own_summaries(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
+    return with_own_output(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
         check_alt_maps(sel.alt, &grid, 1);
         std::vector<PlaneSet> sets(1);
         sets[0].coarse = coarse;
@@ -6257,7 +6247,7 @@ extern "C" int lgs_rtcsm_optimize_pose_query_cost(lgs_ctx* ctx, const lgs_grid* 
     if (const int rc = cost_select(cost, &sel)) return rc;
     if (!sel.alt) return lgs_rtcsm_optimize_pose_query(ctx, grid, params, sel.ge, scan, initial, out);
     if (!ctx || !grid || !params || !out || !scan) return LGS_ERR_INVALID_ARG;
-    return with_own_summaries(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
+    return with_own_output(ctx, out, 1, [&](lgs_rtcsm_summary* o) {
         check_alt_maps(sel.alt, &grid, 1);
         std::vector<PlaneSet> sets(1);
         sets[0].fine = grid;
@@ -6277,7 +6267,7 @@ extern "C" int lgs_rtcsm_optimize_pose_query_batch_cost(lgs_ctx* ctx, const lgs_
     if (!sel.alt) return lgs_rtcsm_optimize_pose_query_batch(ctx, grids, params, sel.ge, scans, initial, n, out);
     if (!ctx || !grids || !params || !scans || !initial || !out || n < 0) return LGS_ERR_INVALID_ARG;
     if (n == 0) return LGS_OK;
-    return with_own_summaries(ctx, out, n, [&](lgs_rtcsm_summary* o) {
+    return with_own_output(ctx, out, n, [&](lgs_rtcsm_summary* o) {
         std::vector<PlaneSet> sets((size_t)n);
         std::vector<int> set_of((size_t)n);
         for (int j = 0; j < n; ++j) {
@@ -6440,21 +6430,11 @@ static int loop_detect_rtcsm_run(lgs_ctx* ctx, const lgs_rtcsm_params* params, c
         num_candidates < 0 || (num_candidates > 0 && (!candidates || !results)))
         return LGS_ERR_INVALID_ARG;
     return guarded(ctx, [&] {
-        LGS_REQUIRE(score_threshold > 0.0 && score_threshold <= 1.0,
-                    "score threshold must be in (0, 1] (:21-22)");
-        int covered = 0;
-        for (int q = 0; q < num_queries; ++q) {
-            const lgs_loop_query& Q = queries[q];
-            LGS_REQUIRE(Q.map, "loop query without a local map");
-            if (alt) check_alt_maps(alt, &Q.map, 1);
-            LGS_REQUIRE(Q.first_candidate == covered && Q.num_candidates >= 0 &&
-                            Q.first_candidate + Q.num_candidates <= num_candidates,
-                        "loop queries must cover the candidates contiguously and in order");
-            covered += Q.num_candidates;
-            for (int j = 0; j < Q.num_candidates; ++j)
-                LGS_REQUIRE(candidates[Q.first_candidate + j].scan, "loop candidate without a scan");
-        }
-        LGS_REQUIRE(covered == num_candidates, "loop queries must cover every candidate");
+        const std::vector<int> query_of =
+            check_loop_batch(score_threshold, queries, num_queries, candidates, num_candidates, ":21-22");
+        // this matcher's own rule: the maps' caps of the square-error and exact costs
+        if (alt)
+            for (int q = 0; q < num_queries; ++q) check_alt_maps(alt, &queries[q].map, 1);
         // group the queries by map geometry (one batch shape per group)
         std::vector<bool> done((size_t)num_queries, false);
         for (int q0 = 0; q0 < num_queries; ++q0) {
@@ -6487,26 +6467,8 @@ static int loop_detect_rtcsm_run(lgs_ctx* ctx, const lgs_rtcsm_params* params, c
             std::vector<lgs_rtcsm_summary> sums(cand.size());
             run_chunked(ctx, params, cost, grids.data(), scans.data(), poses.data(), (int)cand.size(),
                         score_threshold, sets, set_of.data(), sums.data(), alt);
-            for (size_t k = 0; k < cand.size(); ++k) {
-                const int ci = cand[k];
-                int qi = 0;
-                while (!(ci >= queries[qi].first_candidate &&
-                         ci < queries[qi].first_candidate + queries[qi].num_candidates))
-                    ++qi;
-                const lgs_loop_query& Q = queries[qi];
-                lgs_loop_result& r = results[ci];
-                std::memset(&r, 0, sizeof(r));
-                const lgs_rtcsm_summary& s = sums[k];
-                r.found = s.pose_found;
-                r.start_node_index = Q.local_map_node_index;
-                r.end_node_index = candidates[ci].node_index;
-                r.start_node_pose = Q.local_map_node_pose;
-                r.estimated_pose = s.estimated_pose;
-                r.score = s.score_max;
-                r.normalized_cost = s.normalized_cost;
-                if (s.pose_found) r.relative_pose = inverse_compound(Q.local_map_node_pose, s.estimated_pose);
-                std::memcpy(r.covariance, s.covariance, sizeof(r.covariance));
-            }
+            for (size_t k = 0; k < cand.size(); ++k)
+                fill_loop_result(results[cand[k]], queries[query_of[(size_t)cand[k]]], candidates[cand[k]], sums[k]);
         }
     });
 }
@@ -6533,13 +6495,10 @@ extern "C" int lgs_loop_detect_rtcsm_cost(lgs_ctx* ctx, const lgs_rtcsm_params* 
         return lgs_loop_detect_rtcsm(ctx, params, sel.ge, score_threshold, queries, num_queries, candidates,
                                      num_candidates, results);
     if (num_candidates < 0 || (num_candidates > 0 && !results)) return LGS_ERR_INVALID_ARG;
-    std::vector<lgs_loop_result> tmp;
-    const int rc0 = guarded(ctx, [&] { tmp.resize((size_t)num_candidates); });
-    if (rc0 != LGS_OK) return rc0;
-    const int rc = loop_detect_rtcsm_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries,
-                                         candidates, num_candidates, tmp.data());
-    if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
-    return rc;
+    return with_own_output(ctx, results, num_candidates, [&](lgs_loop_result* o) {
+        return loop_detect_rtcsm_run(ctx, params, sel.ge, sel.alt, score_threshold, queries, num_queries, candidates,
+                                     num_candidates, o);
+    });
 }
 
 namespace {
@@ -6697,19 +6656,7 @@ static int loop_detect_rtcsm_multi_run(lgs_ctx* const* ctxs, int num_ctx, const 
     return guarded(c0, [&] {
         // the single-context contract first, so a bad batch fails the same way
         // whatever the shard boundaries (:21-22, queries covering the candidates)
-        LGS_REQUIRE(score_threshold > 0.0 && score_threshold <= 1.0, "score threshold must be in (0, 1] (:21-22)");
-        int covered = 0;
-        for (int q = 0; q < num_queries; ++q) {
-            const lgs_loop_query& Q = queries[q];
-            LGS_REQUIRE(Q.map, "loop query without a local map");
-            LGS_REQUIRE(Q.first_candidate == covered && Q.num_candidates >= 0 &&
-                            Q.first_candidate + Q.num_candidates <= num_candidates,
-                        "loop queries must cover the candidates contiguously and in order");
-            covered += Q.num_candidates;
-            for (int j = 0; j < Q.num_candidates; ++j)
-                LGS_REQUIRE(candidates[Q.first_candidate + j].scan, "loop candidate without a scan");
-        }
-        LGS_REQUIRE(covered == num_candidates, "loop queries must cover every candidate");
+        check_loop_batch(score_threshold, queries, num_queries, candidates, num_candidates, ":21-22");
         const int N = std::min(num_ctx, num_candidates);
         std::vector<LoopShard> shards((size_t)N);
         for (int k = 0; k < N; ++k) {   // contiguous shards, as the gloo/RCCL path
@@ -6770,13 +6717,10 @@ extern "C" int lgs_loop_detect_rtcsm_multi_cost(lgs_ctx* const* ctxs, int num_ct
                                            candidates, num_candidates, results);
     if (!ctxs || num_ctx < 1 || !ctxs[0] || num_candidates < 0 || (num_candidates > 0 && !results))
         return LGS_ERR_INVALID_ARG;
-    std::vector<lgs_loop_result> tmp;
-    const int rc0 = guarded(ctxs[0], [&] { tmp.resize((size_t)num_candidates); });
-    if (rc0 != LGS_OK) return rc0;
-    const int rc = loop_detect_rtcsm_multi_run(ctxs, num_ctx, params, sel.ge, sel.alt, score_threshold, queries,
-                                               num_queries, candidates, num_candidates, tmp.data());
-    if (rc == LGS_OK && num_candidates > 0) std::memcpy(results, tmp.data(), sizeof(lgs_loop_result) * tmp.size());
-    return rc;
+    return with_own_output(ctxs[0], results, num_candidates, [&](lgs_loop_result* o) {
+        return loop_detect_rtcsm_multi_run(ctxs, num_ctx, params, sel.ge, sel.alt, score_threshold, queries,
+                                           num_queries, candidates, num_candidates, o);
+    });
 }
 
 extern "C" int lgs_debug_offset_checks(lgs_ctx* ctx, int reset, unsigned long long* out)

@@ -5,6 +5,13 @@
 //   scan      ranges[n], angles[n] fp64 (SoA, as ScanData<double>)
 //   indices   int2 idx[T][Nv] projected hit cells per search angle (ComputeScanIndices)
 //   scores    coarse fp64 cscore[T*ncx*ncy] in reference block order (t, xc, yc)
+//
+// Also here: LGS_HIP_CHECK, the contexts' scratch arena, uploads, `guarded`
+// (exceptions -> status codes) and `with_own_output` (a `_cost` entry's results
+// reach the caller only on success).  What needs no HIP runtime is in headers
+// of its own, included below: lgs_error.hpp (lgs::Error, LGS_REQUIRE),
+// pose_host.hpp (the host pose algebra) and, for the loop detectors,
+// loop_host.hpp (their batch contract and result record).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +23,7 @@
 #include <functional>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <memory>
 #include <map>
 #include <mutex>
@@ -25,25 +33,16 @@
 #include <vector>
 
 #include "lgs_hip.h"
+#include "lgs_error.hpp"   // lgs::Error, LGS_REQUIRE
+#include "pose_host.hpp"   // ref_sincos, compound, move_backward, inverse_compound
 
 namespace lgs {
-
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 #define LGS_HIP_CHECK(expr)                                                              \
     do {                                                                                 \
         hipError_t e_ = (expr);                                                          \
         if (e_ != hipSuccess)                                                            \
             throw ::lgs::Error(LGS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-#define LGS_REQUIRE(cond, msg)                                                           \
-    do {                                                                                 \
-        if (!(cond))                                                                     \
-            throw ::lgs::Error(LGS_ERR_INVALID_ARG, msg);                                \
     } while (0)
 
 // Scratch slots of the per-context device arena.
@@ -689,38 +688,7 @@ struct lgs_scan {
     mutable double hits_key[5] = { NAN, NAN, NAN, NAN, NAN };
 };
 
-extern "C" void sincos(double x, double* s, double* c);  // glibc
-
 namespace lgs {
-
-// The reference is built with GCC, which fuses sin(x) and cos(x) of the same
-// argument into one glibc sincos() call; glibc's sincos differs from separate
-// sin/cos in ~0.1% of inputs.  Every host recomputation that must be
-// bit-exact therefore calls sincos() explicitly wherever the reference
-// evaluates both (HitPoint, Compound, MoveBackward, ...).
-inline void ref_sincos(double x, double& s, double& c) { ::sincos(x, &s, &c); }
-
-// Host pose algebra restated from H/pose.hpp (glibc sincos, no contraction).
-inline lgs_pose2d compound(lgs_pose2d s, lgs_pose2d d)
-{
-    double sinT, cosT;
-    ref_sincos(s.theta, sinT, cosT);
-    return { cosT * d.x - sinT * d.y + s.x, sinT * d.x + cosT * d.y + s.y, s.theta + d.theta };
-}
-inline lgs_pose2d move_backward(lgs_pose2d e, lgs_pose2d d)
-{
-    const double theta = e.theta - d.theta;
-    double sinT, cosT;
-    ref_sincos(theta, sinT, cosT);
-    return { e.x - cosT * d.x + sinT * d.y, e.y - sinT * d.x - cosT * d.y, theta };
-}
-inline lgs_pose2d inverse_compound(lgs_pose2d s, lgs_pose2d e)
-{
-    double sinT, cosT;
-    ref_sincos(s.theta, sinT, cosT);
-    const double dx = e.x - s.x, dy = e.y - s.y;
-    return { cosT * dx + sinT * dy, -sinT * dx + cosT * dy, e.theta - s.theta };
-}
 
 const int* scan_valid_indices(lgs_ctx* ctx, lgs_scan* scan, double scan_range_max, int* nv);
 // Device copies of the scans' ranges/angles, ordered before the ctx stream's
@@ -879,6 +847,24 @@ int guarded(lgs_ctx* ctx, F&& f)
         if (ctx) ctx->last_error = e.what();
         return LGS_ERR_INTERNAL;
     }
+}
+
+// f(o) computes n records into a buffer o of its own; `out` receives them
+// only when the call succeeds, so a failing call leaves it as it found it.
+// f throws, or returns a status of its own (a guarded call's).
+template <class T, class F>
+int with_own_output(lgs_ctx* ctx, T* out, int n, F&& f)
+{
+    std::vector<T> tmp;
+    int rc = LGS_OK;
+    const int rg = guarded(ctx, [&] {
+        tmp.resize((size_t)n);
+        if constexpr (std::is_void_v<decltype(f(tmp.data()))>) f(tmp.data());
+        else rc = f(tmp.data());
+    });
+    if (rg != LGS_OK) rc = rg;
+    if (rc == LGS_OK && n > 0) std::memcpy(out, tmp.data(), sizeof(T) * (size_t)n);
+    return rc;
 }
 
 // The cost step of a search when it is not the greedy-endpoint stage with its

@@ -669,6 +669,51 @@ void GridMapHip::Download(std::vector<double>* cells, std::vector<uint32_t>* hit
                 "lgs_map_download");
 }
 
+// ------------------------------------------------------------ loop detectors
+namespace {
+
+// The Detect() of every loop detector: the queries and their candidate nodes
+// as the C-ABI's arrays, one call, and the detected loops appended in query ->
+// node order (the reference appends only those).  coarse_of(q) is the query's
+// coarse map handle (null: the detector takes none); call(qs, cs, out) makes
+// the C call.
+template <class CoarseOf, class Call>
+void detect_loops(std::vector<LoopDetectionQuery>& queries, std::vector<LoopDetectionResult>& results,
+                  CoarseOf&& coarse_of, Call&& call)
+{
+    results.clear();
+    if (queries.empty()) return;
+    std::vector<lgs_loop_query> qs;
+    std::vector<lgs_loop_candidate> cs;
+    for (auto& q : queries) {
+        lgs_loop_query c{};
+        c.coarse = coarse_of(q);
+        c.map = q.mLocalMap->Handle();
+        c.local_map_node_pose = to_c(q.mLocalMapNodePose);
+        c.local_map_node_index = q.mLocalMapNodeIndex;
+        c.first_candidate = (int)cs.size();
+        c.num_candidates = (int)q.mPoseGraphNodes.size();
+        qs.push_back(c);
+        for (const auto& n : q.mPoseGraphNodes)
+            cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
+    }
+    std::vector<lgs_loop_result> out(cs.size());
+    call(qs, cs, out);
+    for (const auto& r : out) {
+        if (!r.found) continue;
+        LoopDetectionResult o;
+        o.mRelativePose = from_c(r.relative_pose);
+        o.mStartNodePose = from_c(r.start_node_pose);
+        o.mStartNodeIdx = r.start_node_index;
+        o.mEndNodeIdx = r.end_node_index;
+        o.mEstimatedCovMat = cov_of(r.covariance);
+        results.push_back(o);
+    }
+}
+const lgs_grid* no_coarse(const LoopDetectionQuery&) { return nullptr; }
+
+}  // namespace
+
 // ------------------------------------------ LoopDetectorRealTimeCorrelativeHip
 LoopDetectorRealTimeCorrelativeHip::LoopDetectorRealTimeCorrelativeHip(
     std::shared_ptr<ScanMatcherRealTimeCorrelativeHip> m, double thr, std::vector<DevicePtr> extra)
@@ -683,43 +728,23 @@ LoopDetectorRealTimeCorrelativeHip::LoopDetectorRealTimeCorrelativeHip(
 void LoopDetectorRealTimeCorrelativeHip::Detect(std::vector<LoopDetectionQuery>& queries,
                                                 std::vector<LoopDetectionResult>& results)
 {
-    results.clear();
-    if (queries.empty()) return;
-    const DevicePtr& dev = mScanMatcher->Dev();
-    std::vector<lgs_loop_query> qs;
-    std::vector<lgs_loop_candidate> cs;
-    for (auto& q : queries) {
-        if (!q.mPrecomputedMap)   // LocalMapInfo caches the coarse map (:52-60)
-            q.mPrecomputedMap = std::make_shared<DeviceGrid>(mScanMatcher->ComputeCoarserMap(*q.mLocalMap));
-        lgs_loop_query c{};
-        c.map = q.mLocalMap->Handle();
-        c.coarse = q.mPrecomputedMap->Handle();
-        c.local_map_node_pose = to_c(q.mLocalMapNodePose);
-        c.local_map_node_index = q.mLocalMapNodeIndex;
-        c.first_candidate = (int)cs.size();
-        c.num_candidates = (int)q.mPoseGraphNodes.size();
-        qs.push_back(c);
-        for (const auto& n : q.mPoseGraphNodes)
-            cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
-    }
-    std::vector<lgs_loop_result> out(cs.size());
-    std::vector<lgs_ctx*> ctxs{ dev->Handle() };
-    for (const auto& d : mExtraDevices) ctxs.push_back(d->Handle());
-    const lgs_cost_spec spec = spec_of(*mScanMatcher);
-    dev->Check(lgs_loop_detect_rtcsm_multi_cost(ctxs.data(), (int)ctxs.size(), &mScanMatcher->Params(), &spec,
-                                                mScoreThreshold, qs.data(), (int)qs.size(), cs.data(),
-                                                (int)cs.size(), out.data()),
-               "lgs_loop_detect_rtcsm_multi_cost");
-    for (const auto& r : out) {
-        if (!r.found) continue;   // the reference appends only detected loops, in order (:77-88)
-        LoopDetectionResult o;
-        o.mRelativePose = from_c(r.relative_pose);
-        o.mStartNodePose = from_c(r.start_node_pose);
-        o.mStartNodeIdx = r.start_node_index;
-        o.mEndNodeIdx = r.end_node_index;
-        o.mEstimatedCovMat = cov_of(r.covariance);
-        results.push_back(o);
-    }
+    detect_loops(
+        queries, results,
+        [&](LoopDetectionQuery& q) {
+            if (!q.mPrecomputedMap)   // LocalMapInfo caches the coarse map (:52-60)
+                q.mPrecomputedMap = std::make_shared<DeviceGrid>(mScanMatcher->ComputeCoarserMap(*q.mLocalMap));
+            return q.mPrecomputedMap->Handle();
+        },
+        [&](auto& qs, auto& cs, auto& out) {   // detected loops in order (:77-88)
+            const DevicePtr& dev = mScanMatcher->Dev();
+            std::vector<lgs_ctx*> ctxs{ dev->Handle() };
+            for (const auto& d : mExtraDevices) ctxs.push_back(d->Handle());
+            const lgs_cost_spec spec = spec_of(*mScanMatcher);
+            dev->Check(lgs_loop_detect_rtcsm_multi_cost(ctxs.data(), (int)ctxs.size(), &mScanMatcher->Params(), &spec,
+                                                        mScoreThreshold, qs.data(), (int)qs.size(), cs.data(),
+                                                        (int)cs.size(), out.data()),
+                       "lgs_loop_detect_rtcsm_multi_cost");
+        });
 }
 
 // ------------------------------------------------ LoopDetectorBranchBoundHip
@@ -733,37 +758,14 @@ LoopDetectorBranchBoundHip::LoopDetectorBranchBoundHip(std::shared_ptr<ScanMatch
 void LoopDetectorBranchBoundHip::Detect(std::vector<LoopDetectionQuery>& queries,
                                         std::vector<LoopDetectionResult>& results)
 {
-    results.clear();
-    if (queries.empty()) return;
-    const DevicePtr& dev = mScanMatcher->Dev();
-    std::vector<lgs_loop_query> qs;
-    std::vector<lgs_loop_candidate> cs;
-    for (auto& q : queries) {
-        lgs_loop_query c{};
-        c.map = q.mLocalMap->Handle();   // lgs_loop_detect_bb builds the pyramid (:45-55)
-        c.local_map_node_pose = to_c(q.mLocalMapNodePose);
-        c.local_map_node_index = q.mLocalMapNodeIndex;
-        c.first_candidate = (int)cs.size();
-        c.num_candidates = (int)q.mPoseGraphNodes.size();
-        qs.push_back(c);
-        for (const auto& n : q.mPoseGraphNodes)
-            cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
-    }
-    std::vector<lgs_loop_result> out(cs.size());
-    const lgs_cost_spec spec = spec_of(*mScanMatcher);
-    dev->Check(lgs_loop_detect_bb_cost(dev->Handle(), &mScanMatcher->Params(), &spec, mScoreThreshold, qs.data(),
-                                       (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
-               "lgs_loop_detect_bb_cost");
-    for (const auto& r : out) {
-        if (!r.found) continue;   // only detected loops, in query -> node order (:61-84)
-        LoopDetectionResult o;
-        o.mRelativePose = from_c(r.relative_pose);
-        o.mStartNodePose = from_c(r.start_node_pose);
-        o.mStartNodeIdx = r.start_node_index;
-        o.mEndNodeIdx = r.end_node_index;
-        o.mEstimatedCovMat = cov_of(r.covariance);
-        results.push_back(o);
-    }
+    // lgs_loop_detect_bb builds each map's pyramid (:45-55); detected loops in order (:61-84)
+    detect_loops(queries, results, no_coarse, [&](auto& qs, auto& cs, auto& out) {
+        const DevicePtr& dev = mScanMatcher->Dev();
+        const lgs_cost_spec spec = spec_of(*mScanMatcher);
+        dev->Check(lgs_loop_detect_bb_cost(dev->Handle(), &mScanMatcher->Params(), &spec, mScoreThreshold, qs.data(),
+                                           (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
+                   "lgs_loop_detect_bb_cost");
+    });
 }
 
 // ------------------------------------------------- LoopDetectorGridSearchHip
@@ -777,37 +779,13 @@ LoopDetectorGridSearchHip::LoopDetectorGridSearchHip(std::shared_ptr<ScanMatcher
 void LoopDetectorGridSearchHip::Detect(std::vector<LoopDetectionQuery>& queries,
                                        std::vector<LoopDetectionResult>& results)
 {
-    results.clear();
-    if (queries.empty()) return;
-    const DevicePtr& dev = mScanMatcher->Dev();
-    std::vector<lgs_loop_query> qs;
-    std::vector<lgs_loop_candidate> cs;
-    for (auto& q : queries) {
-        lgs_loop_query c{};
-        c.map = q.mLocalMap->Handle();
-        c.local_map_node_pose = to_c(q.mLocalMapNodePose);
-        c.local_map_node_index = q.mLocalMapNodeIndex;
-        c.first_candidate = (int)cs.size();
-        c.num_candidates = (int)q.mPoseGraphNodes.size();
-        qs.push_back(c);
-        for (const auto& n : q.mPoseGraphNodes)
-            cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
-    }
-    std::vector<lgs_loop_result> out(cs.size());
-    const lgs_cost_spec spec = spec_of(*mScanMatcher);
-    dev->Check(lgs_loop_detect_gs_cost(dev->Handle(), &mScanMatcher->Params(), &spec, mScoreThreshold, qs.data(),
-                                       (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
-               "lgs_loop_detect_gs_cost");
-    for (const auto& r : out) {
-        if (!r.found) continue;   // only detected loops, in query -> node order (:58-80)
-        LoopDetectionResult o;
-        o.mRelativePose = from_c(r.relative_pose);
-        o.mStartNodePose = from_c(r.start_node_pose);
-        o.mStartNodeIdx = r.start_node_index;
-        o.mEndNodeIdx = r.end_node_index;
-        o.mEstimatedCovMat = cov_of(r.covariance);
-        results.push_back(o);
-    }
+    detect_loops(queries, results, no_coarse, [&](auto& qs, auto& cs, auto& out) {   // loops in order (:58-80)
+        const DevicePtr& dev = mScanMatcher->Dev();
+        const lgs_cost_spec spec = spec_of(*mScanMatcher);
+        dev->Check(lgs_loop_detect_gs_cost(dev->Handle(), &mScanMatcher->Params(), &spec, mScoreThreshold, qs.data(),
+                                           (int)qs.size(), cs.data(), (int)cs.size(), out.data()),
+                   "lgs_loop_detect_gs_cost");
+    });
 }
 
 }  // namespace Hip

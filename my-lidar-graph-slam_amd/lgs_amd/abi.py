@@ -653,32 +653,28 @@ class Context:
         return Scan(self, s, r, a, scan.rel_pose, scan.min_range, scan.max_range)
 
     # ---- matcher ----
+    def _call_cost(self, name: str, args: list, i: int):
+        """lgs_<name> with args[i], a CostGEParams, passed by reference; any
+        other cost goes to lgs_<name>_cost as its CostSpec.  Raises unless LGS_OK."""
+        cost = args[i]
+        if not _is_ge(cost):
+            name, cost = name + "_cost", cost_spec(cost)
+        args[i] = C.byref(cost)
+        self.check(getattr(self.lib, "lgs_" + name)(*args), name)
+
     def optimize_pose(self, grid, coarse, params: RtcsmParams, cost: CostGEParams, scan, init,
                       thr: float) -> RtcsmSummary:
         """cost: a CostGEParams (the greedy-endpoint entry point) or a CostSQParams / CostSpec (its `_cost` twin);
         the same holds for every matcher and loop-detector method below"""
         out = RtcsmSummary()
-        if not _is_ge(cost):
-            rc = self.lib.lgs_rtcsm_optimize_pose_cost(self.h, grid.h, coarse.h, C.byref(params),
-                                                       C.byref(cost_spec(cost)), scan.h, Pose2D(*init), float(thr),
-                                                       C.byref(out))
-            self.check(rc, "rtcsm_optimize_pose_cost")
-            return out
-        rc = self.lib.lgs_rtcsm_optimize_pose(self.h, grid.h, coarse.h, C.byref(params), C.byref(cost), scan.h,
-                                              Pose2D(*init), float(thr), C.byref(out))
-        self.check(rc, "rtcsm_optimize_pose")
+        self._call_cost("rtcsm_optimize_pose", [self.h, grid.h, coarse.h, C.byref(params), cost, scan.h,
+                                                Pose2D(*init), float(thr), C.byref(out)], 4)
         return out
 
     def optimize_pose_query(self, grid, params: RtcsmParams, cost: CostGEParams, scan, init) -> RtcsmSummary:
         out = RtcsmSummary()
-        if not _is_ge(cost):
-            rc = self.lib.lgs_rtcsm_optimize_pose_query_cost(self.h, grid.h, C.byref(params), C.byref(cost_spec(cost)),
-                                                             scan.h, Pose2D(*init), C.byref(out))
-            self.check(rc, "rtcsm_optimize_pose_query_cost")
-            return out
-        rc = self.lib.lgs_rtcsm_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
-                                                    Pose2D(*init), C.byref(out))
-        self.check(rc, "rtcsm_optimize_pose_query")
+        self._call_cost("rtcsm_optimize_pose_query", [self.h, grid.h, C.byref(params), cost, scan.h, Pose2D(*init),
+                                                      C.byref(out)], 3)
         return out
 
     def optimize_pose_query_batch(self, grids, params: RtcsmParams, cost: CostGEParams, scans, inits):
@@ -691,14 +687,7 @@ class Context:
         sarr = (_P * n)(*[s.h for s in scans])
         poses = (Pose2D * n)(*[Pose2D(*p) for p in inits])
         out = (RtcsmSummary * n)()
-        if not _is_ge(cost):
-            rc = self.lib.lgs_rtcsm_optimize_pose_query_batch_cost(self.h, garr, C.byref(params),
-                                                                   C.byref(cost_spec(cost)), sarr, poses, n, out)
-            self.check(rc, "rtcsm_optimize_pose_query_batch_cost")
-            return list(out)
-        rc = self.lib.lgs_rtcsm_optimize_pose_query_batch(self.h, garr, C.byref(params), C.byref(cost), sarr,
-                                                          poses, n, out)
-        self.check(rc, "rtcsm_optimize_pose_query_batch")
+        self._call_cost("rtcsm_optimize_pose_query_batch", [self.h, garr, C.byref(params), cost, sarr, poses, n, out], 3)
         return list(out)
 
     def optimize_pose_batch(self, grid, coarse, params, cost, scans: Sequence["Scan"], inits, thr: float):
@@ -706,14 +695,8 @@ class Context:
         arr = (_P * n)(*[s.h for s in scans])
         poses = (Pose2D * n)(*[Pose2D(*p) for p in inits])
         out = (RtcsmSummary * n)()
-        if not _is_ge(cost):
-            rc = self.lib.lgs_rtcsm_optimize_pose_batch_cost(self.h, grid.h, coarse.h, C.byref(params),
-                                                             C.byref(cost_spec(cost)), arr, poses, n, float(thr), out)
-            self.check(rc, "rtcsm_optimize_pose_batch_cost")
-            return list(out)
-        rc = self.lib.lgs_rtcsm_optimize_pose_batch(self.h, grid.h, coarse.h, C.byref(params), C.byref(cost),
-                                                    arr, poses, n, float(thr), out)
-        self.check(rc, "rtcsm_optimize_pose_batch")
+        self._call_cost("rtcsm_optimize_pose_batch", [self.h, grid.h, coarse.h, C.byref(params), cost, arr, poses, n,
+                                                      float(thr), out], 4)
         return list(out)
 
     def dense_scores(self, grid, coarse, params, scan, init):
@@ -729,38 +712,31 @@ class Context:
         return list(dims), cs, fs
 
     # ---- loop-closure batch ----
+    @staticmethod
+    def _loop_arrays(queries, candidates, coarse: bool):
+        """the (LoopQuery, LoopCandidate, LoopResult) arrays of a loop batch;
+        coarse: pass a query's coarse grid on (else the detector ignores it)"""
+        qs = (LoopQuery * max(1, len(queries)))()
+        for i, (m, c, pose, idx, first, cnt) in enumerate(queries):
+            qs[i] = LoopQuery(m.h, c.h if coarse and c is not None else None, Pose2D(*pose), idx, first, cnt)
+        cs = (LoopCandidate * max(1, len(candidates)))()
+        for i, (s, pose, idx) in enumerate(candidates):
+            cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
+        return qs, cs, (LoopResult * max(1, len(candidates)))()
+
     def loop_detect(self, params: RtcsmParams, cost: CostGEParams, thr: float, queries, candidates,
                     shards: Sequence["Context"] = ()):
         """queries: [(map Grid, coarse Grid|None, node_pose, node_index, first, count)];
         candidates: [(Scan, node_pose, node_index)] -> ctypes LoopResult array (one per candidate).
         shards: further contexts (GPUs) to split the candidates over
         (lgs_loop_detect_rtcsm_multi; this context is shard 0)."""
-        qs = (LoopQuery * max(1, len(queries)))()
-        for i, (m, c, pose, idx, first, cnt) in enumerate(queries):
-            qs[i] = LoopQuery(m.h, c.h if c is not None else None, Pose2D(*pose), idx, first, cnt)
-        cs = (LoopCandidate * max(1, len(candidates)))()
-        for i, (s, pose, idx) in enumerate(candidates):
-            cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
-        out = (LoopResult * max(1, len(candidates)))()
+        qs, cs, out = self._loop_arrays(queries, candidates, True)
+        tail = [C.byref(params), cost, float(thr), qs, len(queries), cs, len(candidates), out]
         if shards:
             hs = (_P * (1 + len(shards)))(self.h, *[c.h for c in shards])
-            if not _is_ge(cost):
-                self.check(self.lib.lgs_loop_detect_rtcsm_multi_cost(hs, len(hs), C.byref(params),
-                                                                     C.byref(cost_spec(cost)), float(thr), qs,
-                                                                     len(queries), cs, len(candidates), out),
-                           "loop_detect_rtcsm_multi_cost")
-                return out
-            self.check(self.lib.lgs_loop_detect_rtcsm_multi(hs, len(hs), C.byref(params), C.byref(cost), float(thr),
-                                                            qs, len(queries), cs, len(candidates), out),
-                       "loop_detect_rtcsm_multi")
-            return out
-        if not _is_ge(cost):
-            self.check(self.lib.lgs_loop_detect_rtcsm_cost(self.h, C.byref(params), C.byref(cost_spec(cost)), float(thr),
-                                                           qs, len(queries), cs, len(candidates), out),
-                       "loop_detect_rtcsm_cost")
-            return out
-        self.check(self.lib.lgs_loop_detect_rtcsm(self.h, C.byref(params), C.byref(cost), float(thr), qs,
-                                                  len(queries), cs, len(candidates), out), "loop_detect_rtcsm")
+            self._call_cost("loop_detect_rtcsm_multi", [hs, len(hs)] + tail, 3)
+        else:
+            self._call_cost("loop_detect_rtcsm", [self.h] + tail, 2)
         return out
 
     # ---- the loop batch over several processes (RCCL) ----
@@ -805,41 +781,21 @@ class Context:
         sarr = (_P * n)(*[s.h for s in scans])
         poses = (Pose2D * n)(*[Pose2D(*p) for p in inits])
         out = (RtcsmSummary * max(1, n))()
-        if not _is_ge(cost):
-            self.check(self.lib.lgs_bb_optimize_pose_batch_cost(self.h, grid.h, parr, C.byref(params),
-                                                                C.byref(cost_spec(cost)), sarr, poses, n, float(thr),
-                                                                out), "bb_optimize_pose_batch_cost")
-            return list(out)[:n]
-        self.check(self.lib.lgs_bb_optimize_pose_batch(self.h, grid.h, parr, C.byref(params), C.byref(cost), sarr,
-                                                       poses, n, float(thr), out), "bb_optimize_pose_batch")
+        self._call_cost("bb_optimize_pose_batch", [self.h, grid.h, parr, C.byref(params), cost, sarr, poses, n,
+                                                   float(thr), out], 4)
         return list(out)[:n]
 
     def bb_optimize_pose_query(self, grid, params: "BBParams", cost: CostGEParams, scan, init) -> RtcsmSummary:
         out = RtcsmSummary()
-        if not _is_ge(cost):
-            self.check(self.lib.lgs_bb_optimize_pose_query_cost(self.h, grid.h, C.byref(params),
-                                                                C.byref(cost_spec(cost)), scan.h, Pose2D(*init),
-                                                                C.byref(out)), "bb_optimize_pose_query_cost")
-            return out
-        self.check(self.lib.lgs_bb_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
-                                                       Pose2D(*init), C.byref(out)), "bb_optimize_pose_query")
+        self._call_cost("bb_optimize_pose_query", [self.h, grid.h, C.byref(params), cost, scan.h, Pose2D(*init),
+                                                   C.byref(out)], 3)
         return out
 
     def loop_detect_bb(self, params: "BBParams", cost: CostGEParams, thr: float, queries, candidates):
         """as loop_detect, with LoopDetectorBranchBound (the coarse entry of a query is ignored)"""
-        qs = (LoopQuery * max(1, len(queries)))()
-        for i, (m, c, pose, idx, first, cnt) in enumerate(queries):
-            qs[i] = LoopQuery(m.h, None, Pose2D(*pose), idx, first, cnt)
-        cs = (LoopCandidate * max(1, len(candidates)))()
-        for i, (s, pose, idx) in enumerate(candidates):
-            cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
-        out = (LoopResult * max(1, len(candidates)))()
-        if not _is_ge(cost):
-            self.check(self.lib.lgs_loop_detect_bb_cost(self.h, C.byref(params), C.byref(cost_spec(cost)), float(thr), qs,
-                                                        len(queries), cs, len(candidates), out), "loop_detect_bb_cost")
-            return out
-        self.check(self.lib.lgs_loop_detect_bb(self.h, C.byref(params), C.byref(cost), float(thr), qs,
-                                               len(queries), cs, len(candidates), out), "loop_detect_bb")
+        qs, cs, out = self._loop_arrays(queries, candidates, False)
+        self._call_cost("loop_detect_bb", [self.h, C.byref(params), cost, float(thr), qs, len(queries), cs,
+                                           len(candidates), out], 2)
         return out
 
     # ---- exhaustive grid-search matcher ----
@@ -848,24 +804,14 @@ class Context:
         sarr = (_P * max(1, n))(*[s.h for s in scans])
         poses = (Pose2D * max(1, n))(*[Pose2D(*p) for p in inits])
         out = (RtcsmSummary * max(1, n))()
-        if not _is_ge(cost):
-            self.check(self.lib.lgs_gs_optimize_pose_batch_cost(self.h, grid.h, C.byref(params),
-                                                                C.byref(cost_spec(cost)), sarr, poses, n, float(thr),
-                                                                out), "gs_optimize_pose_batch_cost")
-            return list(out)[:n]
-        self.check(self.lib.lgs_gs_optimize_pose_batch(self.h, grid.h, C.byref(params), C.byref(cost), sarr, poses,
-                                                       n, float(thr), out), "gs_optimize_pose_batch")
+        self._call_cost("gs_optimize_pose_batch", [self.h, grid.h, C.byref(params), cost, sarr, poses, n, float(thr),
+                                                   out], 3)
         return list(out)[:n]
 
     def gs_optimize_pose_query(self, grid, params: "GSParams", cost: CostGEParams, scan, init) -> RtcsmSummary:
         out = RtcsmSummary()
-        if not _is_ge(cost):
-            self.check(self.lib.lgs_gs_optimize_pose_query_cost(self.h, grid.h, C.byref(params),
-                                                                C.byref(cost_spec(cost)), scan.h, Pose2D(*init),
-                                                                C.byref(out)), "gs_optimize_pose_query_cost")
-            return out
-        self.check(self.lib.lgs_gs_optimize_pose_query(self.h, grid.h, C.byref(params), C.byref(cost), scan.h,
-                                                       Pose2D(*init), C.byref(out)), "gs_optimize_pose_query")
+        self._call_cost("gs_optimize_pose_query", [self.h, grid.h, C.byref(params), cost, scan.h, Pose2D(*init),
+                                                   C.byref(out)], 3)
         return out
 
     def gs_dense_scores(self, grid, params: "GSParams", scan, init) -> np.ndarray:
@@ -880,19 +826,9 @@ class Context:
 
     def loop_detect_gs(self, params: "GSParams", cost: CostGEParams, thr: float, queries, candidates):
         """as loop_detect, with LoopDetectorGridSearch (the coarse entry of a query is ignored)"""
-        qs = (LoopQuery * max(1, len(queries)))()
-        for i, (m, c, pose, idx, first, cnt) in enumerate(queries):
-            qs[i] = LoopQuery(m.h, None, Pose2D(*pose), idx, first, cnt)
-        cs = (LoopCandidate * max(1, len(candidates)))()
-        for i, (s, pose, idx) in enumerate(candidates):
-            cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
-        out = (LoopResult * max(1, len(candidates)))()
-        if not _is_ge(cost):
-            self.check(self.lib.lgs_loop_detect_gs_cost(self.h, C.byref(params), C.byref(cost_spec(cost)), float(thr), qs,
-                                                        len(queries), cs, len(candidates), out), "loop_detect_gs_cost")
-            return out
-        self.check(self.lib.lgs_loop_detect_gs(self.h, C.byref(params), C.byref(cost), float(thr), qs,
-                                               len(queries), cs, len(candidates), out), "loop_detect_gs")
+        qs, cs, out = self._loop_arrays(queries, candidates, False)
+        self._call_cost("loop_detect_gs", [self.h, C.byref(params), cost, float(thr), qs, len(queries), cs,
+                                           len(candidates), out], 2)
         return out
 
     # ---- hill-climbing matcher ----
