@@ -1127,9 +1127,12 @@ void map_resize(lgs_map* m, double minX, double minY, double maxX, double maxY)
 // Resize followed by Reset (ConstructMapFromScans :288-290): every cell ends
 // up zero, so nothing is copied and an allocation that is large enough is
 // reused.
-void map_resize_reset(lgs_map* m, double minX, double minY, double maxX, double maxY)
+//
+// map_reset_storage is its storage half: room for g's cells, all zero; the
+// geometry and the patch flags stay (the allocation never shrinks, so the
+// old geometry still fits).  palloc_remap + map_set_geom complete it.
+void map_reset_storage(lgs_map* m, const ResizeGeom& g)
 {
-    const ResizeGeom g = resize_geom(m, minX, minY, maxX, maxY);
     const size_t need = std::max<size_t>(1, (size_t)g.w * g.h);
     hipStream_t st = m->ctx->stream;
     if (need > m->cap) {
@@ -1149,6 +1152,13 @@ void map_resize_reset(lgs_map* m, double minX, double minY, double maxX, double 
         m->d_miss = (uint32_t*)((char*)m->d_cells + 12 * need);
         LGS_HIP_CHECK(hipMemsetAsync(m->d_cells, 0, need * 16, st));
     }
+    m->view.d = m->d_cells;
+}
+
+void map_resize_reset(lgs_map* m, double minX, double minY, double maxX, double maxY)
+{
+    const ResizeGeom g = resize_geom(m, minX, minY, maxX, maxY);
+    map_reset_storage(m, g);
     palloc_remap(m, g);   // Reset keeps the patches allocated (grid_map_patch.hpp:194-203)
     map_set_geom(m, g);
 }
@@ -1582,9 +1592,11 @@ void raycast_maps(lgs_ctx* ctx, std::vector<MapJob>& jobs, const lgs_builder_par
 // the hit points, boxes, ray cells and key offsets formed on the device
 // (k_hits, k_raycells): the host keeps the geometry
 // (Resize) between the two device phases, from the boxes k_hits returns --
-// identical values, so identical maps.  Returns false, with the maps as they
-// were or resized and reset for the same boxes, when the pass does not fit
-// one emit/sort/apply pass or an angle lies outside gl_sincos's domain: the
+// identical values, so identical maps.  Returns false, with the maps'
+// geometry and patch flags as they were (not resized: the host path's Resize
+// must be each map's only one; their cells may be zeroed already, as that
+// Resize + Reset leaves them), when the pass does not fit one
+// emit/sort/apply pass or an angle lies outside gl_sincos's domain: the
 // caller then runs the host path.
 bool construct_maps_device(lgs_ctx* ctx, lgs_map* const* maps, const int* first, const int* count, int n_maps,
                            const lgs_scan* const* scans, const lgs_pose2d* poses, const lgs_builder_params* bp)
@@ -1662,7 +1674,13 @@ bool construct_maps_device(lgs_ctx* ctx, lgs_map* const* maps, const int* first,
     }
     if (bad) return false;
     // the maps' boxes as ConstructMapFromScans accumulates them (:234-285;
-    // topRight starts at numeric_limits<double>::min()), then Resize + Reset
+    // topRight starts at numeric_limits<double>::min()) and the geometry
+    // Resize will give each map.  The maps keep their geometry and patch
+    // flags until the pass is known to fit: Resize is not idempotent (a box
+    // that starts on cell -k PatchSize gets the patch before it as well,
+    // :905-915, which a second Resize to the same box drops), so the host
+    // path must find them unresized.  Only Reset's zeroing runs ahead (it
+    // overlaps the round trip for the key total; the host path repeats it).
     std::vector<std::array<double, 4>> box(n_maps, std::array<double, 4>{ DBL_MAX, DBL_MAX, DBL_MIN, DBL_MIN });
     for (int u = 0; u < nu; ++u) {
         auto& b = box[units[u].job];
@@ -1671,7 +1689,6 @@ bool construct_maps_device(lgs_ctx* ctx, lgs_map* const* maps, const int* first,
         b[2] = smax(b[2], ubox[u][2]);
         b[3] = smax(b[3], ubox[u][3]);
     }
-    for (int j = 0; j < n_maps; ++j) map_resize_reset(maps[j], box[j][0], box[j][1], box[j][2], box[j][3]);
     // phase 2: ray cells, ray -> map, key offsets
     std::vector<int> ray0(nu);
     long long nr = 0;
@@ -1679,32 +1696,31 @@ bool construct_maps_device(lgs_ctx* ctx, lgs_map* const* maps, const int* first,
         ray0[u] = (int)nr;
         nr += cnt[u];
     }
-    std::vector<RayMap> rm(n_maps);
     std::vector<MapGeo> geo(n_maps);
+    std::vector<ResizeGeom> rg(n_maps);
     unsigned long long cells = 0;
     for (int j = 0; j < n_maps; ++j) {
         const lgs_map* m = maps[j];
-        rm[j] = RayMap{ cells, m->w, m->h, m->d_cells, m->d_hit, m->d_miss, m->d_palloc, m->ps, m->npx };
-        geo[j] = MapGeo{ m->min_x, m->min_y, m->res };
-        cells += (unsigned long long)m->w * m->h;
+        const ResizeGeom g = rg[j] = resize_geom(m, box[j][0], box[j][1], box[j][2], box[j][3]);
+        // map_set_geom's minimum
+        geo[j] = MapGeo{ m->min_x + (g.pminx * m->ps) * m->res, m->min_y + (g.pminy * m->ps) * m->res, m->res };
+        cells += (unsigned long long)g.w * g.h;
     }
     if (nr == 0 || nr >= (1LL << 30) || cells >= (1ull << 31)) return false;
+    for (int j = 0; j < n_maps; ++j) map_reset_storage(maps[j], rg[j]);
     const bool multi = n_maps > 1;
-    const BayesChains chains = make_chains(bp->prob_hit, bp->prob_miss);
-    Upload up(ctx);
-    const size_t uo = up.append(units.data(), units.size());
-    const size_t go = up.append(geo.data(), geo.size());
-    const size_t ro = up.append(ray0.data(), ray0.size());
-    const size_t co = up.append(&chains, 1);
-    const size_t mo = up.append(rm.data(), rm.size());
-    up.flush();
-    hipLaunchKernelGGL(k_raycells, dim3(nu), dim3(256), 0, st, up.at<HitUnit>(uo), (const double2*)d_hits, d_cnt,
-                       up.at<MapGeo>(go), up.at<int>(ro), d_rays, d_offs, multi ? d_rmap : nullptr, d_ukeys);
-    hipLaunchKernelGGL(k_unit_scan, dim3(1), dim3(256), 0, st, d_ukeys, nu, d_kbase, d_total);
-    hipLaunchKernelGGL(k_addbase, dim3(nu), dim3(256), 0, st, d_cnt, up.at<int>(ro), d_kbase, d_offs);
-    LGS_HIP_CHECK(hipGetLastError());
     long long keys = 0;
     {
+        Upload up(ctx);
+        const size_t uo = up.append(units.data(), units.size());
+        const size_t go = up.append(geo.data(), geo.size());
+        const size_t ro = up.append(ray0.data(), ray0.size());
+        up.flush();
+        hipLaunchKernelGGL(k_raycells, dim3(nu), dim3(256), 0, st, up.at<HitUnit>(uo), (const double2*)d_hits, d_cnt,
+                           up.at<MapGeo>(go), up.at<int>(ro), d_rays, d_offs, multi ? d_rmap : nullptr, d_ukeys);
+        hipLaunchKernelGGL(k_unit_scan, dim3(1), dim3(256), 0, st, d_ukeys, nu, d_kbase, d_total);
+        hipLaunchKernelGGL(k_addbase, dim3(nu), dim3(256), 0, st, d_cnt, up.at<int>(ro), d_kbase, d_offs);
+        LGS_HIP_CHECK(hipGetLastError());
         char* pin = (char*)ctx->ensure_pinned(16);
         LGS_HIP_CHECK(hipMemcpyAsync(pin, d_total, 8, hipMemcpyDeviceToHost, st));
         ctx->sync();
@@ -1712,7 +1728,23 @@ bool construct_maps_device(lgs_ctx* ctx, lgs_map* const* maps, const int* first,
     }
     const long long budget = std::max(1LL, std::min(ctx->ray_chunk_keys, 1LL << 30));
     if (keys > budget) return false;
-    // phase 3: emit, sort, runs, apply -- raycast_maps' pass
+    // the rest of Resize + Reset (:288-290), then phase 3: emit, sort, runs, apply -- raycast_maps' pass
+    std::vector<RayMap> rm(n_maps);
+    cells = 0;
+    for (int j = 0; j < n_maps; ++j) {
+        lgs_map* m = maps[j];
+        palloc_remap(m, rg[j]);
+        map_set_geom(m, rg[j]);
+        if (m->min_x != geo[j].min_x || m->min_y != geo[j].min_y)
+            throw Error(LGS_ERR_INTERNAL, "map geometry differs from the ray cells'");
+        rm[j] = RayMap{ cells, m->w, m->h, m->d_cells, m->d_hit, m->d_miss, m->d_palloc, m->ps, m->npx };
+        cells += (unsigned long long)m->w * m->h;
+    }
+    const BayesChains chains = make_chains(bp->prob_hit, bp->prob_miss);
+    Upload up(ctx);
+    const size_t co = up.append(&chains, 1);
+    const size_t mo = up.append(rm.data(), rm.size());
+    up.flush();
     const RayMap* d_maps = up.at<RayMap>(mo);
     const BayesChains* d_chains = up.at<BayesChains>(co);
     unsigned* d_keys = (unsigned*)ctx->ensure(S_RAY2, sizeof(unsigned) * keys);
