@@ -1159,6 +1159,95 @@ int  lgs_icp_ref_optimize_pose_batch(lgs_ctx* ctx, const lgs_icp_ref* const* ref
 int  lgs_icp_ref_pairs(lgs_ctx* ctx, const lgs_icp_ref* ref, const lgs_scan* scan, lgs_pose2d sensor_pose,
                        const lgs_icp_params* params, int* ref_index, int* beam_index, double* residual);
 
+/* ---- nearest-node loop searcher (k_loop_search.hip) ----
+ * LoopSearcherNearest::Search (C/mapping/loop_searcher_nearest.cpp:13-108) over
+ * flat arrays, batched over hints.  A graph snapshot is poses[n] (node k has
+ * index k) and m local maps with inclusive node ranges idx_min[i] <= idx_max[i]
+ * < n (they may overlap and need not be contiguous: the convention of
+ * lgs_maps_construct_from_scans).  The walk is the list of positions (map i,
+ * node k), i = 0 .. m - 2, k = idx_min[i] .. idx_max[i], in that order;
+ * travel[p] is the reference's nodeTravelDist after position p (t = 0,
+ * prev = poses[0]; per position t += hypot(prev.x - x, prev.y - y), prev =
+ * pose), formed on the host with the C library's hypot.
+ * Per hint: only the positions of maps 0 .. num_maps - 2 are walked; cut is
+ * the lowest of them with accum_travel_dist - travel[p] < travel_dist_threshold
+ * (or their count); the winner is the lowest position p < cut that minimises
+ * d2 = (x_k - x_r) * (x_k - x_r) + (y_k - y_r) * (y_k - y_r) (r the latest node;
+ * no contraction) among those with d2 < pow(node_dist_threshold, 2.0).
+ * Device, host function and reference agree byte for byte, whatever the
+ * tiling: the reduction is an argmin under a strict <.
+ * LGS_ERR_INVALID_ARG, before any device work: a NULL argument (per_map
+ * apart), n < 1, m < 1, n, m, q or the walk's length above 2^27, a range outside
+ * [0, n) or idx_min > idx_max, a non-finite pose x / y, threshold or
+ * accum_travel_dist, num_candidate_nodes < 0, num_maps outside 1 .. m,
+ * latest_local_map_idx outside [0, num_maps), a latest node outside [0, n) or
+ * outside its latest local map's range.  A failing call writes nothing. */
+typedef struct {
+    int latest_node_idx;        /* LoopSearchHint::mLatestNodeIdx */
+    int latest_local_map_idx;   /* mLatestLocalMapIdx */
+    int num_maps;               /* mLocalMapPositions.size(): 1 .. m */
+    int pad_;                   /* 0 */
+    double accum_travel_dist;   /* mAccumTravelDist */
+} lgs_loop_search_hint;
+/* LoopSearcherNearest's constructor arguments */
+typedef struct {
+    double travel_dist_threshold;
+    double node_dist_threshold;
+    int num_candidate_nodes;
+    int pad_;
+} lgs_loop_search_params;
+/* One record per hint; every byte is defined, so records compare bytewise.
+ * Nothing found: found = 0, the four indices -1, dist_sq = pow(node_dist_threshold, 2.0). */
+typedef struct {
+    int found;
+    int local_map_idx;          /* LoopCandidate::mLocalMapIdx */
+    int local_map_node_idx;     /* mLocalMapNodeIdx */
+    int node_idx_min;           /* mNodeIndices = node_idx_min .. node_idx_max: */
+    int node_idx_max;           /* max(latest map's min, latest - K), min(its max, latest + K) */
+    int walked;                 /* cut */
+    double dist_sq;             /* the winner's d2 */
+} lgs_loop_search_result;
+/* Per-map table entry: the lowest-position minimiser inside one map's segment
+ * of the walk under the same cut and threshold; none = {-1, 0, pow(thr, 2.0)}.
+ * Row j * m + i is hint j's entry for map i; maps the hint does not walk
+ * (num_maps - 1 .. m - 1) hold none.  The record's winner is the lowest map
+ * with the strictly smallest dist_sq of its hint's row. */
+typedef struct {
+    int node_idx;
+    int pad_;
+    double dist_sq;
+} lgs_loop_search_map_best;
+typedef struct lgs_loop_graph lgs_loop_graph;
+/* The snapshot behind a handle: the walk and travel[] are formed here, on the
+ * host, and uploaded once.  Copies what it needs.  The handle belongs to ctx
+ * and, like an lgs_grid, may be destroyed after it. */
+int  lgs_loop_graph_create(lgs_ctx* ctx, const lgs_pose2d* poses, int n, const int* idx_min, const int* idx_max,
+                           int m, lgs_loop_graph** out);
+void lgs_loop_graph_destroy(lgs_loop_graph* graph);
+/* Nodes, maps, walk positions and travel[positions - 1] (0 for an empty walk); each may be NULL */
+int  lgs_loop_graph_info(const lgs_loop_graph* graph, int* n, int* m, int* positions, double* walk_travel);
+/* Diagnostics: travel[0 .. positions) into out (cap doubles at least positions) */
+int  lgs_loop_graph_travel(const lgs_loop_graph* graph, double* out, int cap);
+/* q hints against the snapshot: results[q], and per_map[q * m] unless NULL.
+ * Below LGS_OPT_LOOP_SEARCH_MIN_PAIRS hint x position pairs the host loop runs
+ * instead of the kernels (same bytes).  q = 0 is legal. */
+int  lgs_loop_search_nearest(lgs_loop_graph* graph, const lgs_loop_search_params* params,
+                             const lgs_loop_search_hint* hints, int q, lgs_loop_search_result* results,
+                             lgs_loop_search_map_best* per_map);
+/* The reference's loop, statement for statement, per hint: no context, no GPU */
+int  lgs_loop_search_nearest_host(const lgs_pose2d* poses, int n, const int* idx_min, const int* idx_max, int m,
+                                  const lgs_loop_search_params* params, const lgs_loop_search_hint* hints, int q,
+                                  lgs_loop_search_result* results, lgs_loop_search_map_best* per_map);
+/* GridMapBuilder::UpdateAccumTravelDist (C/mapping/grid_map_builder.cpp:210-224):
+ * the hypot chain over all nodes, on the host */
+int  lgs_pg_accum_travel_dist(const lgs_pose2d* poses, int n, double* out);
+/* Searches on this context since its creation: out4 = {calls that ran the
+ * kernels, calls that ran the host loop, kernel launches, hint x position
+ * pairs of the device calls} */
+int  lgs_loop_search_stats(const lgs_ctx* ctx, long long* out4);
+#define LGS_OPT_LOOP_SEARCH_MIN_PAIRS 39 /* lgs_loop_search_nearest: calls of fewer hint x walk-position pairs run the host loop instead of launching (default 65536, the measured crossover rounded down to a power of two); 0 = always the device */
+#define LGS_OPT_LOOP_SEARCH_GROUP     40 /* tests: walk positions per workgroup group of the search's main pass (groups are whole maps; results do not depend on it; a size that gives more than 65535 groups is doubled until they fit); 0 (default) = chosen from the walk's length and the hint count */
+
 #ifdef __cplusplus
 }
 #endif

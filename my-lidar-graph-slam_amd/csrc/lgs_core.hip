@@ -196,7 +196,7 @@ const char* const kKernelNames[K_NUM_KERNELS] = { "k_project", "k_coarse", "k_se
                                                   "k_linsolve", "k_ray_emit", "k_ray_apply",
                                                   "k_super", "k_super_planes", "k_bb_score", "k_bb_expand",
                                                   "k_coarse_aux", "k_match_small", "k_gs_score", "k_cost_sq",
-                                                  "k_cost_gx" };
+                                                  "k_cost_gx", "k_loop_search" };
 }
 
 int lgs_ctx::next_stamp()
@@ -553,6 +553,14 @@ extern "C" int lgs_ctx_set_option(lgs_ctx* ctx, int option, double value)
     case LGS_OPT_PGCG_GRID_NODES:
         if (!(value >= 0.0)) return LGS_ERR_INVALID_ARG;
         ctx->pg_grid_nodes = (int)std::min(value, 2147483647.0);
+        return LGS_OK;
+    case LGS_OPT_LOOP_SEARCH_MIN_PAIRS:
+        if (!(value >= 0.0)) return LGS_ERR_INVALID_ARG;
+        ctx->loop_min_pairs = (long long)std::min(value, 9.0e18);
+        return LGS_OK;
+    case LGS_OPT_LOOP_SEARCH_GROUP:
+        if (!(value >= 0.0)) return LGS_ERR_INVALID_ARG;
+        ctx->loop_group = (int)std::min(value, 134217728.0);
         return LGS_OK;
     case LGS_OPT_SEED_WIDE:
         if (!(value >= 0.0 && value <= 16.0)) return LGS_ERR_INVALID_ARG;

@@ -92,6 +92,7 @@ enum Slot {
     S_PG2, S_PG3,   // resident pose-graph LM (k_pglm.hip): incidence lists and edges; poses, loss terms, step record
     S_ICP0, S_ICP1, // point-to-line ICP (k_icp.hip): records, trajectory, error word; lgs_icp_pairs' outputs
     S_ICPR0,        // lgs_icp_ref_create (k_icp_ref.hip): per-scan boxes and the cell counts of a build
+    S_LOOPS0, S_LOOPS1,   // loop search (k_loop_search.hip): cuts and group partials; records and the per-map table
     // bank 1 of the per-batch buffers: a batched call keeps two 64-query
     // chunks in flight (the next chunk's launches go out before the host
     // finishes the previous one), each in its own bank (lgs_ctx::banked)
@@ -257,6 +258,7 @@ enum KernelId { K_PROJECT = 0, K_COARSE, K_SEED, K_SELECT, K_FINE, K_REPLAY, K_C
                 K_GS_SCORE,     // k_gs_score: the grid-search matcher's score + workgroup argmax pass
                 K_COST_SQ,      // k_cost_sq: the correlative pipeline's square-error cost stage
                 K_COST_GX,      // k_cost_gx: the correlative pipeline's exact greedy-endpoint cost stage
+                K_LOOP_SEARCH,  // k_loop_cut + k_loop_main + k_loop_combine: the nearest-node loop searcher
                 K_NUM_KERNELS };
 extern const char* const kKernelNames[K_NUM_KERNELS];
 struct PendingTiming {
@@ -439,6 +441,12 @@ struct lgs_ctx {
     long long pg_solves = 0, pg_iterations = 0, pg_patterns = 0, pg_grid_solves = 0;
     int pg_grid_nodes = 1280;    // graphs from this many nodes on solve over many workgroups (LGS_OPT_PGCG_GRID_NODES)
     hipEvent_t pg_ev[2] = {};    // the multi-workgroup solve's chunk records
+    // lgs_loop_search_nearest (k_loop_search.hip): hint x position pairs below which the host loop runs
+    // (LGS_OPT_LOOP_SEARCH_MIN_PAIRS), positions per group (LGS_OPT_LOOP_SEARCH_GROUP; 0 = chosen per
+    // call) and the counters of lgs_loop_search_stats
+    long long loop_min_pairs = 65536;
+    int loop_group = 0;
+    long long loop_device_calls = 0, loop_host_calls = 0, loop_launches = 0, loop_pairs = 0;
     // lgs_pg_lm_optimize (k_pglm.hip): the counters of lgs_pg_lm_stats
     long long pglm_optimizes = 0, pglm_steps = 0, pglm_pose_uploads = 0, pglm_pose_downloads = 0, pglm_incidence_builds = 0;
     // padded phase-plane buffer (per bank): margins zeroed once per (buffer, layout, set count)

@@ -788,5 +788,134 @@ void LoopDetectorGridSearchHip::Detect(std::vector<LoopDetectionQuery>& queries,
     });
 }
 
+// ---------------------------------------------------- LoopSearcherNearestHip
+namespace {
+
+void snapshot_arrays(const std::vector<RobotPose2D<double>>& nodes, const std::vector<LocalMapNodeRange>& maps,
+                     std::vector<lgs_pose2d>& poses, std::vector<int>& lo, std::vector<int>& hi)
+{
+    poses.reserve(nodes.size());
+    for (const auto& p : nodes) poses.push_back(to_c(p));
+    for (const auto& m : maps) {
+        lo.push_back(m.mPoseGraphNodeIdxMin);
+        hi.push_back(m.mPoseGraphNodeIdxMax);
+    }
+}
+
+std::vector<lgs_loop_search_hint> batch_hints(const std::vector<LoopSearchBatchHint>& hints)
+{
+    std::vector<lgs_loop_search_hint> hs;
+    hs.reserve(hints.size());
+    for (const auto& h : hints)
+        hs.push_back({ h.mLatestNodeIdx, h.mLatestLocalMapIdx, h.mNumOfMaps, 0, h.mAccumTravelDist });
+    return hs;
+}
+
+// nodeIndices = nodeIdxMin .. nodeIdxMax (:100-102)
+LoopCandidate candidate_of(const lgs_loop_search_result& r, int mapIdx, int mapNodeIdx)
+{
+    LoopCandidate c;
+    c.mNodeIndices.resize((size_t)(r.node_idx_max - r.node_idx_min + 1));
+    for (size_t i = 0; i < c.mNodeIndices.size(); ++i) c.mNodeIndices[i] = r.node_idx_min + (int)i;
+    c.mLocalMapIdx = mapIdx;
+    c.mLocalMapNodeIdx = mapNodeIdx;
+    return c;
+}
+
+}  // namespace
+
+LoopGraphHip::LoopGraphHip(DevicePtr dev, const std::vector<RobotPose2D<double>>& nodes,
+                           const std::vector<LocalMapNodeRange>& maps)
+    : mDev(std::move(dev)), mNumOfNodes((int)nodes.size()), mNumOfMaps((int)maps.size())
+{
+    std::vector<lgs_pose2d> poses;
+    std::vector<int> lo, hi;
+    snapshot_arrays(nodes, maps, poses, lo, hi);
+    mDev->Check(lgs_loop_graph_create(mDev->Handle(), poses.data(), mNumOfNodes, lo.data(), hi.data(), mNumOfMaps,
+                                      &mGraph),
+                "lgs_loop_graph_create");
+}
+
+LoopGraphHip::~LoopGraphHip()
+{
+    if (mGraph) lgs_loop_graph_destroy(mGraph);
+}
+
+LoopSearcherNearestHip::LoopSearcherNearestHip(double travelDistThreshold, double nodeDistThreshold,
+                                               int numOfCandidateNodes)
+{
+    mParams.travel_dist_threshold = travelDistThreshold;
+    mParams.node_dist_threshold = nodeDistThreshold;
+    mParams.num_candidate_nodes = numOfCandidateNodes;
+    mParams.pad_ = 0;
+}
+
+LoopCandidateVector LoopSearcherNearestHip::Search(const LoopSearchHint& hint) const
+{
+    std::vector<lgs_pose2d> poses;
+    std::vector<int> lo, hi;
+    snapshot_arrays(hint.mPoseGraphNodes, hint.mLocalMapPositions, poses, lo, hi);
+    const lgs_loop_search_hint h = { hint.mLatestNodeIdx, hint.mLatestLocalMapIdx, (int)lo.size(), 0,
+                                     hint.mAccumTravelDist };
+    lgs_loop_search_result r;
+    const int rc = lgs_loop_search_nearest_host(poses.data(), (int)poses.size(), lo.data(), hi.data(), (int)lo.size(),
+                                                &mParams, &h, 1, &r, nullptr);
+    if (rc != LGS_OK) throw Error(rc, "lgs_loop_search_nearest_host: invalid loop search hint");
+    LoopCandidateVector out;
+    if (r.found) out.push_back(candidate_of(r, r.local_map_idx, r.local_map_node_idx));
+    return out;
+}
+
+std::vector<LoopCandidateVector> LoopSearcherNearestHip::SearchBatch(const LoopGraphHip& graph,
+                                                                     const std::vector<LoopSearchBatchHint>& hints) const
+{
+    const std::vector<lgs_loop_search_hint> hs = batch_hints(hints);
+    std::vector<lgs_loop_search_result> res(hs.size());
+    std::vector<LoopCandidateVector> out(hs.size());
+    if (hs.empty()) return out;
+    graph.Dev()->Check(lgs_loop_search_nearest(graph.Handle(), &mParams, hs.data(), (int)hs.size(), res.data(), nullptr),
+                       "lgs_loop_search_nearest");
+    for (size_t j = 0; j < hs.size(); ++j)
+        if (res[j].found) out[j].push_back(candidate_of(res[j], res[j].local_map_idx, res[j].local_map_node_idx));
+    return out;
+}
+
+std::vector<LoopCandidateVector> LoopSearcherNearestHip::SearchAllMaps(const LoopGraphHip& graph,
+                                                                       const std::vector<LoopSearchBatchHint>& hints) const
+{
+    const std::vector<lgs_loop_search_hint> hs = batch_hints(hints);
+    const size_t m = (size_t)graph.NumOfMaps();
+    std::vector<lgs_loop_search_result> res(hs.size());
+    std::vector<lgs_loop_search_map_best> rows(hs.size() * m);
+    std::vector<LoopCandidateVector> out(hs.size());
+    if (hs.empty()) return out;
+    graph.Dev()->Check(lgs_loop_search_nearest(graph.Handle(), &mParams, hs.data(), (int)hs.size(), res.data(),
+                                               rows.data()),
+                       "lgs_loop_search_nearest");
+    for (size_t j = 0; j < hs.size(); ++j)
+        for (size_t i = 0; i < m && res[j].found; ++i)
+            if (rows[j * m + i].node_idx >= 0) out[j].push_back(candidate_of(res[j], (int)i, rows[j * m + i].node_idx));
+    return out;
+}
+
+std::vector<LoopDetectionQuery> GetLoopDetectionQueries(const LoopCandidateVector& loopCandidates,
+                                                        const std::vector<LoopCandidateNode>& nodes,
+                                                        const std::vector<DeviceGridPtr>& localMaps)
+{
+    std::vector<LoopDetectionQuery> queries;
+    queries.reserve(loopCandidates.size());
+    for (const LoopCandidate& c : loopCandidates) {
+        LoopDetectionQuery q;
+        q.mPoseGraphNodes.reserve(c.mNodeIndices.size());
+        for (const int k : c.mNodeIndices) q.mPoseGraphNodes.push_back(nodes.at((size_t)k));
+        q.mLocalMap = localMaps.at((size_t)c.mLocalMapIdx);
+        const LoopCandidateNode& node = nodes.at((size_t)c.mLocalMapNodeIdx);
+        q.mLocalMapNodePose = node.mPose;
+        q.mLocalMapNodeIndex = node.mIndex;
+        queries.push_back(std::move(q));
+    }
+    return queries;
+}
+
 }  // namespace Hip
 }  // namespace MyLidarGraphSlam

@@ -543,5 +543,80 @@ private:
     double mScoreThreshold;
 };
 
+// LoopSearcherNearest (C/mapping/loop_searcher_nearest.cpp:13-108; lgs_loop_*,
+// DESIGN.md §4.6g).  LoopSearchHint and LoopCandidate are H/mapping/
+// loop_searcher.hpp:24-82 with vectors in place of the std::maps: node k at
+// index k, local map i at index i.
+struct LocalMapNodeRange {
+    int mPoseGraphNodeIdxMin = 0, mPoseGraphNodeIdxMax = 0;   // LocalMapPosition's, inclusive
+};
+struct LoopSearchHint {
+    std::vector<RobotPose2D<double>> mPoseGraphNodes;
+    std::vector<LocalMapNodeRange> mLocalMapPositions;
+    double mAccumTravelDist = 0.0;
+    int mLatestNodeIdx = 0;
+    int mLatestLocalMapIdx = 0;
+};
+struct LoopCandidate {
+    std::vector<int> mNodeIndices;
+    int mLocalMapIdx = 0;
+    int mLocalMapNodeIdx = 0;
+};
+using LoopCandidateVector = std::vector<LoopCandidate>;
+
+// A graph snapshot on the device (lgs_loop_graph): the poses of all nodes and
+// the node ranges of all local maps, the last one the latest, unfinished map.
+class LoopGraphHip {
+public:
+    LoopGraphHip(DevicePtr dev, const std::vector<RobotPose2D<double>>& poseGraphNodes,
+                 const std::vector<LocalMapNodeRange>& localMapPositions);
+    ~LoopGraphHip();
+    LoopGraphHip(const LoopGraphHip&) = delete;
+    LoopGraphHip& operator=(const LoopGraphHip&) = delete;
+    lgs_loop_graph* Handle() const { return mGraph; }
+    int NumOfNodes() const { return mNumOfNodes; }
+    int NumOfMaps() const { return mNumOfMaps; }
+    const DevicePtr& Dev() const { return mDev; }
+
+private:
+    DevicePtr mDev;
+    lgs_loop_graph* mGraph = nullptr;
+    int mNumOfNodes = 0, mNumOfMaps = 0;
+};
+
+// One hint of a batch against a snapshot: what LoopSearchHint holds besides the snapshot
+struct LoopSearchBatchHint {
+    int mLatestNodeIdx = 0;
+    int mLatestLocalMapIdx = 0;
+    int mNumOfMaps = 0;              // mLocalMapPositions.size() when the node was the latest one
+    double mAccumTravelDist = 0.0;
+};
+
+class LoopSearcherNearestHip {
+public:
+    LoopSearcherNearestHip(double travelDistThreshold, double nodeDistThreshold, int numOfCandidateNodes);
+    // the reference's Search: one hint, the loop on the host (no device work);
+    // empty when no node is near
+    LoopCandidateVector Search(const LoopSearchHint& searchHint) const;
+    // many hints against one snapshot on the device: out[j] is Search's answer for hints[j]
+    std::vector<LoopCandidateVector> SearchBatch(const LoopGraphHip& graph,
+                                                 const std::vector<LoopSearchBatchHint>& hints) const;
+    // one LoopCandidate per finished local map the node is near (the nearest
+    // node inside that map), in map order, from the per-map table
+    std::vector<LoopCandidateVector> SearchAllMaps(const LoopGraphHip& graph,
+                                                   const std::vector<LoopSearchBatchHint>& hints) const;
+    const lgs_loop_search_params& Params() const { return mParams; }
+
+private:
+    lgs_loop_search_params mParams{};
+};
+
+// LidarGraphSlam::GetLoopDetectionQueries (C/mapping/lidar_graph_slam.cpp:155-188):
+// per candidate its nodes (nodes[k] is node k), its local map (localMaps[i] is
+// map i) and the local map's node
+std::vector<LoopDetectionQuery> GetLoopDetectionQueries(const LoopCandidateVector& loopCandidates,
+                                                        const std::vector<LoopCandidateNode>& nodes,
+                                                        const std::vector<DeviceGridPtr>& localMaps);
+
 }  // namespace Hip
 }  // namespace MyLidarGraphSlam

@@ -54,6 +54,10 @@ KERNEL_IDS = ["k_project", "k_coarse", "k_seed", "k_select", "k_fine", "k_replay
               "k_linsolve", "k_ray_emit", "k_ray_apply", "k_super", "k_super_planes", "k_bb_score",
               "k_bb_expand", "k_coarse_aux", "k_match_small", "k_gs_score",
               "k_cost_sq", "k_cost_gx"]   # lgs_ctx_kernel_stats order
+# kernels with a statistics slot past the list above (not part of the profile / skip masks built from it)
+MORE_KERNEL_IDS = ["k_loop_search"]
+LGS_OPT_LOOP_SEARCH_MIN_PAIRS = 39  # lgs_loop_search_nearest: hint x position pairs below which the host loop runs (0: always the device)
+LGS_OPT_LOOP_SEARCH_GROUP = 40      # tests: walk positions per workgroup group of the search (0: chosen per call)
 
 
 class Pose2D(C.Structure):
@@ -231,6 +235,27 @@ class IcpSummary(C.Structure):
                 ("covariance", C.c_double * 9), ("sensor_pose", Pose2D), ("best_sensor_pose", Pose2D),
                 ("cost", C.c_double), ("pair_cost", C.c_double), ("initial_cost", C.c_double),
                 ("hessian", C.c_double * 9), ("rhs", C.c_double * 3)]
+
+
+class LoopSearchHint(C.Structure):
+    """lgs_loop_search_hint: one LoopSearchHint of the nearest-node loop searcher."""
+    _fields_ = [("latest_node_idx", C.c_int), ("latest_local_map_idx", C.c_int), ("num_maps", C.c_int),
+                ("pad_", C.c_int), ("accum_travel_dist", C.c_double)]
+
+
+class LoopSearchParams(C.Structure):
+    """lgs_loop_search_params: LoopSearcherNearest's constructor arguments."""
+    _fields_ = [("travel_dist_threshold", C.c_double), ("node_dist_threshold", C.c_double),
+                ("num_candidate_nodes", C.c_int), ("pad_", C.c_int)]
+
+
+class LoopSearchResult(C.Structure):
+    _fields_ = [("found", C.c_int), ("local_map_idx", C.c_int), ("local_map_node_idx", C.c_int),
+                ("node_idx_min", C.c_int), ("node_idx_max", C.c_int), ("walked", C.c_int), ("dist_sq", C.c_double)]
+
+
+class LoopSearchMapBest(C.Structure):
+    _fields_ = [("node_idx", C.c_int), ("pad_", C.c_int), ("dist_sq", C.c_double)]
 
 
 class LoopQuery(C.Structure):
@@ -468,6 +493,17 @@ _PROTOS = [
                                                   C.POINTER(IcpParams), C.POINTER(IcpSummary)]),
     ("lgs_icp_ref_pairs", C.c_int, [_P, _P, _P, Pose2D, C.POINTER(IcpParams), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_double)]),
+    ("lgs_loop_graph_create", C.c_int, [_P, C.POINTER(Pose2D), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                        C.POINTER(_P)]),
+    ("lgs_loop_graph_destroy", None, [_P]),
+    ("lgs_loop_graph_info", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_double)]),
+    ("lgs_loop_graph_travel", C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
+    ("lgs_loop_search_nearest", C.c_int, [_P, C.POINTER(LoopSearchParams), _P, C.c_int, _P, _P]),
+    ("lgs_loop_search_nearest_host", C.c_int, [C.POINTER(Pose2D), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                               C.c_int, C.POINTER(LoopSearchParams), _P, C.c_int, _P, _P]),
+    ("lgs_pg_accum_travel_dist", C.c_int, [C.POINTER(Pose2D), C.c_int, C.POINTER(C.c_double)]),
+    ("lgs_loop_search_stats", C.c_int, [_P, C.POINTER(C.c_longlong)]),
     ("lgs_debug_keysort", C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
     ("lgs_debug_map_rebuilds", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("lgs_debug_copy_counters", C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -477,6 +513,79 @@ _PROTOS = [
 ]
 
 SYMBOLS = [p[0] for p in _PROTOS]
+
+# the loop searcher's records as numpy rows (the layouts of the structs above)
+LOOP_HINT_DTYPE = np.dtype([("latest_node_idx", "<i4"), ("latest_local_map_idx", "<i4"), ("num_maps", "<i4"),
+                            ("pad_", "<i4"), ("accum_travel_dist", "<f8")])
+LOOP_RESULT_DTYPE = np.dtype([("found", "<i4"), ("local_map_idx", "<i4"), ("local_map_node_idx", "<i4"),
+                              ("node_idx_min", "<i4"), ("node_idx_max", "<i4"), ("walked", "<i4"), ("dist_sq", "<f8")])
+LOOP_MAP_BEST_DTYPE = np.dtype([("node_idx", "<i4"), ("pad_", "<i4"), ("dist_sq", "<f8")])
+
+
+def loop_hints(latest_node_idx, latest_local_map_idx, num_maps, accum_travel_dist) -> np.ndarray:
+    """lgs_loop_search_hint rows from four equally long sequences (scalars broadcast)"""
+    a = np.broadcast_arrays(np.asarray(latest_node_idx), np.asarray(latest_local_map_idx), np.asarray(num_maps),
+                            np.asarray(accum_travel_dist, dtype=np.float64))
+    h = np.zeros(a[0].size, dtype=LOOP_HINT_DTYPE)
+    h["latest_node_idx"], h["latest_local_map_idx"], h["num_maps"] = a[0].ravel(), a[1].ravel(), a[2].ravel()
+    h["accum_travel_dist"] = a[3].ravel()
+    return h
+
+
+def _loop_snapshot(poses, idx_min, idx_max):
+    p = np.ascontiguousarray(poses, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] not in (2, 3):
+        raise ValueError("poses: n x 2 (x, y) or n x 3 (x, y, theta)")
+    if p.shape[1] == 2:
+        p = np.ascontiguousarray(np.hstack([p, np.zeros((len(p), 1))]))
+    lo, hi = np.ascontiguousarray(idx_min, dtype=np.int32), np.ascontiguousarray(idx_max, dtype=np.int32)
+    if lo.shape != hi.shape or lo.ndim != 1:
+        raise ValueError("idx_min, idx_max: two equally long index lists")
+    return p, lo, hi
+
+
+def _loop_hint_rows(hints) -> np.ndarray:
+    h = np.ascontiguousarray(hints)
+    if h.dtype != LOOP_HINT_DTYPE:
+        raise ValueError("hints: rows of LOOP_HINT_DTYPE (abi.loop_hints)")
+    return h
+
+
+def _iptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def loop_search_host(poses, idx_min, idx_max, params: "LoopSearchParams", hints, per_map: bool = False):
+    """lgs_loop_search_nearest_host: the reference's loop per hint, no device.
+    Returns the records (LOOP_RESULT_DTYPE rows), with per_map also the q x m
+    table (LOOP_MAP_BEST_DTYPE); raises LgsError on bad arguments."""
+    lib = load()
+    p, lo, hi = _loop_snapshot(poses, idx_min, idx_max)
+    h = _loop_hint_rows(hints)
+    q, m = len(h), len(lo)
+    res = np.zeros(q, dtype=LOOP_RESULT_DTYPE)
+    tab = np.zeros((q, m), dtype=LOOP_MAP_BEST_DTYPE) if per_map else None
+    rc = lib.lgs_loop_search_nearest_host(p.ctypes.data_as(C.POINTER(Pose2D)), len(p), _iptr(lo), _iptr(hi), m,
+                                          C.byref(params), h.ctypes.data, q, res.ctypes.data,
+                                          tab.ctypes.data if per_map else None)
+    if rc != LGS_OK:
+        err = LgsError(f"loop_search_host: status {rc}")
+        err.status = rc
+        raise err
+    return (res, tab) if per_map else res
+
+
+def accum_travel_dist(poses) -> float:
+    """lgs_pg_accum_travel_dist: GridMapBuilder::UpdateAccumTravelDist over all nodes (host)"""
+    lib = load()
+    p, _, _ = _loop_snapshot(poses, [], [])
+    out = C.c_double()
+    rc = lib.lgs_pg_accum_travel_dist(p.ctypes.data_as(C.POINTER(Pose2D)), len(p), C.byref(out))
+    if rc != LGS_OK:
+        err = LgsError(f"accum_travel_dist: status {rc}")
+        err.status = rc
+        raise err
+    return out.value
 
 _lib: Optional[C.CDLL] = None
 
@@ -560,8 +669,9 @@ class Context:
 
     def kernel_stats(self) -> dict:
         """{name: dict(launches, total_ms, algo_bytes)} since the last reset."""
-        buf = (KernelStat * len(KERNEL_IDS))()
-        n = self.lib.lgs_ctx_kernel_stats(self.h, buf, len(KERNEL_IDS))
+        cap = len(KERNEL_IDS) + len(MORE_KERNEL_IDS)
+        buf = (KernelStat * cap)()
+        n = self.lib.lgs_ctx_kernel_stats(self.h, buf, cap)
         if n < 0:
             self.check(-n, "kernel_stats")
         return {buf[i].name.decode(): dict(launches=buf[i].launches, total_ms=buf[i].total_ms,
@@ -938,6 +1048,22 @@ class Context:
         h = _P()
         self.check(self.lib.lgs_icp_ref_create(self.h, arr, ps, n, C.byref(params), C.byref(h)), "icp_ref_create")
         return IcpRef(self, h)
+
+    def loop_graph(self, poses, idx_min, idx_max) -> "LoopGraph":
+        """lgs_loop_graph_create: a graph snapshot (poses n x 2 or n x 3, the
+        maps' inclusive node ranges) for the nearest-node loop searcher
+        (DESIGN.md 4.6g); the walk and its travel chain go to the device once."""
+        p, lo, hi = _loop_snapshot(poses, idx_min, idx_max)
+        h = _P()
+        self.check(self.lib.lgs_loop_graph_create(self.h, p.ctypes.data_as(C.POINTER(Pose2D)), len(p), _iptr(lo),
+                                                  _iptr(hi), len(lo), C.byref(h)), "loop_graph_create")
+        return LoopGraph(self, h, len(lo))
+
+    def loop_search_stats(self) -> dict:
+        """lgs_loop_search_stats: searches of this context that ran the kernels / the host loop"""
+        v = (C.c_longlong * 4)()
+        self.check(self.lib.lgs_loop_search_stats(self.h, v), "loop_search_stats")
+        return dict(device_calls=v[0], host_calls=v[1], launches=v[2], pairs=v[3])
 
     def cost_square_error(self, grid, umin: float, umax: float, scan, sensor_pose, covariance: bool = False):
         v = C.c_double()
@@ -1393,6 +1519,49 @@ class IcpRef:
     def close(self):
         if self.h:
             self.ctx.lib.lgs_icp_ref_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LoopGraph:
+    """lgs_loop_graph: a graph snapshot of the nearest-node loop searcher."""
+    GraphInfo = namedtuple("GraphInfo", "n m positions walk_travel")
+
+    def __init__(self, ctx, h, m):
+        self.ctx, self.h, self.m = ctx, h, m
+
+    def info(self):
+        v = [C.c_int() for _ in range(3)]
+        t = C.c_double()
+        self.ctx.check(self.ctx.lib.lgs_loop_graph_info(self.h, *[C.byref(x) for x in v], C.byref(t)), "loop_graph_info")
+        return LoopGraph.GraphInfo(*[x.value for x in v], t.value)
+
+    def travel(self) -> np.ndarray:
+        """lgs_loop_graph_travel: travel[p] after every walk position"""
+        out = np.zeros(self.info().positions)
+        self.ctx.check(self.ctx.lib.lgs_loop_graph_travel(self.h, dptr(out), len(out)), "loop_graph_travel")
+        return out
+
+    def search(self, params: "LoopSearchParams", hints, per_map: bool = False):
+        """lgs_loop_search_nearest: the records (LOOP_RESULT_DTYPE rows) of the
+        hints (abi.loop_hints), with per_map also the q x m table"""
+        h = _loop_hint_rows(hints)
+        q = len(h)
+        res = np.zeros(q, dtype=LOOP_RESULT_DTYPE)
+        tab = np.zeros((q, self.m), dtype=LOOP_MAP_BEST_DTYPE) if per_map else None
+        self.ctx.check(self.ctx.lib.lgs_loop_search_nearest(self.h, C.byref(params), h.ctypes.data, q, res.ctypes.data,
+                                                            tab.ctypes.data if per_map else None),
+                       "loop_search_nearest")
+        return (res, tab) if per_map else res
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lgs_loop_graph_destroy(self.h)
             self.h = None
 
     def __del__(self):

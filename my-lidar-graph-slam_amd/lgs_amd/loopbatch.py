@@ -53,6 +53,30 @@ class Candidate:
     node_index: int
 
 
+def candidates_from_search(records, scans, poses, local_maps: Sequence[LocalMap]
+                           ) -> Tuple[List[LocalMap], List[Candidate]]:
+    """LidarGraphSlam::GetLoopDetectionQueries (C/mapping/lidar_graph_slam.cpp:155-188)
+    over the loop searcher's records (abi.LOOP_RESULT_DTYPE rows, from
+    LoopGraph.search or abi.loop_search_host): every found record becomes one
+    query, in record order -- the local map records[j].local_map_idx with the
+    node local_map_node_idx as its node -- and its nodes node_idx_min ..
+    node_idx_max become that query's candidates, in node order.
+    scans[k] = (ranges, angles) and poses[k] = (x, y, theta) of node k;
+    local_maps[i] = map i (its node fields are not read; the cells are shared,
+    not copied).  Returns (maps, candidates): candidates[*].query indexes maps,
+    query-major, as hip_detect_fn* and run_sharded take them."""
+    maps: List[LocalMap] = []
+    cands: List[Candidate] = []
+    for r in records:
+        if not r["found"]:
+            continue
+        lm, node = local_maps[int(r["local_map_idx"])], int(r["local_map_node_idx"])
+        maps.append(LocalMap(lm.cells, lm.min_x, lm.min_y, lm.res, tuple(float(v) for v in poses[node]), node))
+        for k in range(int(r["node_idx_min"]), int(r["node_idx_max"]) + 1):
+            cands.append(Candidate(len(maps) - 1, scans[k][0], scans[k][1], tuple(float(v) for v in poses[k]), k))
+    return maps, cands
+
+
 def shard_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:
     """Contiguous block of rank r: sizes differ by at most one."""
     base, rem = divmod(n, world)
