@@ -200,6 +200,7 @@ int  lgs_abi_version(void);
 #define LGS_OPT_PGCG_GRID_NODES 36 /* lgs_pg_cg_solve: systems of at least this many nodes run over many workgroups, two launches per CG pass (default 1280: up to there the vectors of the one-workgroup solve fit LDS and it is the faster one); smaller ones in one persistent workgroup.  0 = always the grid, 2^31 - 1 = never */
 #define LGS_OPT_FAST_ROWS     37  /* 1 (default) = a lean batch's superblock pass forms a wave's 64 hit-point cells with a shorter fp64 chain (csrc/fast_cell.hpp) wherever every lane's cell is certified equal to the exact chain's and unguarded, and with the exact chain otherwise (bit-identical records); 0 = the exact chain always */
 #define LGS_OPT_HV_INZERO     38  /* 1 (default) = a thread of the superblock pass (k_super_hv) whose whole input footprint lies in precompute tiles that read all-(+0) inputs this call (k_hv_inzero: one 64-bit lane mask per set and wave) issues none of its loads; 0 = no mask, every thread loads (A/B inside one build, tests).  Batches of two or more maps only (a lone call is latency-bound and takes no mask); needs LGS_OPT_ZERO_TILES 1 */
+#define LGS_OPT_SELECT_LIST   41  /* batched pruned correlative chunks that take the kept-superblock work list (LGS_OPT_LANES_MIN_BATCH): the largest number of coarse blocks per match (K = angles x blocks per angle) up to which the refine candidates are selected from the listed superblocks' blocks alone, in one launch of one workgroup per match that also writes the dense list (k_select_list); above it, and with 0 = never, k_select rules on every coarse block and k_compact writes the dense list (the same bytes either way).  Default 524288, what the kernel's 64 KB of LDS hold (larger values mean the same) */
 #define LGS_OPT_POISON_WS     15/* diagnostics: 1 = fill every match workspace and record with 0xFF bytes before the batch runs (any read-before-write shows up) */
 int  lgs_ctx_set_option(lgs_ctx* ctx, int option, double value);
 
@@ -213,7 +214,13 @@ int  lgs_ctx_set_option(lgs_ctx* ctx, int option, double value);
  * in-masks of the item's set after the last batch [one u64 per wave of a
  * plane's k_super_hv threads: bit l = lane l loaded nothing; empty when the set
  * had none], 11 its out-masks [lr*lr planes x waves u64: bit l = everything
- * lane l stores holds +0; empty without LGS_OPT_ZERO_TILES]. */
+ * lane l stores holds +0; empty without LGS_OPT_ZERO_TILES].
+ * The selection of the refine candidates (empty for one-block windows):
+ * 12 list [nseg segments of 1024 i32: the first segcnt[s] of segment s are its
+ * selected blocks, ascending], 13 segcnt [nseg i32], 14 nsel [i32] followed
+ * by dlist [K i32: the first nsel are the selected blocks, ascending; empty
+ * when the batch's fine evaluator takes no dense list], 15 one i32: 1 when
+ * k_select_list wrote the item's selection, 0 when k_select (+ k_compact) did. */
 int  lgs_debug_item_buffer(lgs_ctx* ctx, int item, int which, void* out, size_t cap, size_t* bytes);
 
 /* Diagnostics: the device's restatements of glibc's sincos() (op 0: out[2i] =

@@ -3252,6 +3252,138 @@ __global__ __launch_bounds__(256) void k_compact(Items items)
     if (threadIdx.x == 0) *it.nsel = pref[it.nseg];
 }
 
+// k_select_list: k_select + k_compact of a work-list batch from the kept
+// superblocks alone (k_keep's list), one workgroup per item.  k_select rules
+// on every key of the item -- the keep rule again, two 64-bit divisions and a
+// bound read each -- although only the listed superblocks were scored (config
+// 2: ~104 of 10.5 k per item, 1.6 % of the keys).  Here 16 lanes take one
+// listed superblock's member blocks and apply k_select's predicate to those
+// k_coarse_list_c scored (the same `active` test), so cscore / cflag outside
+// the list -- stale or poisoned bytes -- are never read.  The list's order is
+// arbitrary (k_keep's atomics) and the output's is the reference's block
+// order: every selected key sets its bit in a bitmap of the item's nseg *
+// kSelSeg keys in LDS (16 64-bit words per segment, the whole dynamic LDS),
+// and a walk over the words in order gives segcnt[s] (written for every
+// segment, zeros included), list[s * kSelSeg + rank] and, with `dense`
+// (B.fine_lanes: what k_compact wrote), dlist[0..nsel) and nsel.  No sort and
+// no bound on the number of selected keys.  The host takes this kernel only
+// when the batch's largest K fits the bitmap (kSelListMaxK keys = 64 KB).
+constexpr long long kSelListMaxK = 524288;
+// 16 waves: an item's pass is a chain of dependent reads (entry -> score and
+// flag), and the chunk's launch lasts as long as its item with the longest
+// list (most items list ~100 superblocks, one in a chunk often thousands),
+// so the reads in flight decide: 64 entries per row of threads, kSelListU
+// rows per pass, the next pass's entries fetched under this one's scores
+// (traced, config 2, two streams: 256 threads x 4 rows 92 us per launch on
+// average, 339 at most; this shape 25 and 71, k_select<256> + k_compact 48;
+// DESIGN.md §8 also has the split of an item over workgroups, not taken)
+constexpr int kSelListThreads = 1024;
+constexpr int kSelListU = 8;
+__global__ __launch_bounds__(kSelListThreads) void k_select_list(Items items, WorkList W, int dense, DevTs dts)
+{
+    const DtsScopeAll dts_scope(dts);   // uneven workgroups: every one stamps its end
+    extern __shared__ unsigned long long s_bm[];   // nseg * 16 words
+    constexpr int kT = kSelListThreads, kW = kT / 64, kU = kSelListU, kRow = kT / 16;
+    const int j = blockIdx.x;
+    const MatchItem& it = items[j];
+    const RtcsmPlan& pl = it.pl;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int nwords = it.nseg * (kSelSeg / 64);
+    const int* __restrict__ sbl = W.sbl + (size_t)j * W.region;
+    const int cnt = min(W.cnt[16 * j], W.region);
+    int ent[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+        const int e = (tid >> 4) + kRow * u;
+        ent[u] = e < cnt ? sbl[e] : -1;
+    }
+    for (int w = tid; w < nwords; w += kT) s_bm[w] = 0ull;
+    __syncthreads();
+    // 1. the listed superblocks' member blocks, 16 lanes per entry
+    {
+        const double* __restrict__ cscore = it.cscore;
+        const uint8_t* __restrict__ cflag = it.cflag;
+        const double L = *it.Lp, thr = pl.thr;
+        const int nsbx = max(pl.nsbx, 1), m = tid & 15;
+        unsigned* bm32 = (unsigned*)s_bm;
+        for (int e0 = tid >> 4; e0 < cnt; e0 += kRow * kU) {
+            int k[kU];
+            double c[kU];
+            uint8_t fl[kU];
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int t = ent[u] >> 6, sb = ent[u] & 63;
+                const int jx = kSB * (sb % nsbx) + (m & 3), jy = kSB * (sb / nsbx) + (m >> 2);
+                const bool active = ent[u] >= 0 && t < pl.T && jx < pl.ncx && jy < pl.ncy;
+                k[u] = active ? t * pl.P + jx * pl.ncy + jy : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                c[u] = k[u] >= 0 ? cscore[k[u]] : 0.0;
+                fl[u] = k[u] >= 0 ? cflag[k[u]] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int e = e0 + kRow * (kU + u);
+                ent[u] = e < cnt ? sbl[e] : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u)
+                if (k[u] >= 0 && (c[u] > thr) && (fl[u] || c[u] >= L)) atomicOr(bm32 + (k[u] >> 5), 1u << (k[u] & 31));
+        }
+    }
+    __syncthreads();
+    // 2. the words in order, one per thread and pass: a wave's inclusive scan
+    // of their popcounts gives a word's rank in its segment (its 16 words are
+    // 16 consecutive lanes) and the segment's count; the waves' totals
+    // (through LDS) and the passes before give its dense position
+    int* __restrict__ list = it.list;
+    int* __restrict__ dlist = it.dlist;
+    int run = 0;
+    for (int w0 = 0; w0 < nwords; w0 += kT) {   // workgroup-uniform
+        const int w = w0 + tid;
+        unsigned long long v = w < nwords ? s_bm[w] : 0ull;
+        const int c = __popcll(v);
+        int incl = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int u = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += u;
+        }
+        const int excl = incl - c;
+        const int seg0 = __shfl(excl, lane & ~15, 64);      // keys of the wave's earlier segments
+        const int segn = __shfl(incl, lane | 15, 64) - seg0;
+        if ((lane & 15) == 0 && w < nwords) it.segcnt[w >> 4] = segn;   // nwords = 16 nseg: every segment, once
+        int base = 0;
+        if (dense) {
+            // once this pass's words are read their first 64 bytes (a pass
+            // holds whole segments of 128) carry the waves' totals: the
+            // bitmap is all the LDS there is at the largest K, and no pass
+            // reads or writes another pass's words
+            static_assert(kW * sizeof(int) <= (kSelSeg / 64) * sizeof(unsigned long long), "totals fit one segment");
+            __syncthreads();
+            int* wt = (int*)(s_bm + w0);
+            if (lane == 63) wt[wid] = incl;
+            __syncthreads();
+            base = run;
+#pragma unroll
+            for (int q = 0; q < kW; ++q) {
+                const int tq = wt[q];
+                if (q < wid) base += tq;
+                run += tq;
+            }
+        }
+        int r = 0;
+        for (; v; v &= v - 1ull, ++r) {
+            const int key = (w << 6) + __ffsll((long long)v) - 1;
+            list[(size_t)(w >> 4) * kSelSeg + (excl - seg0) + r] = key;
+            if (dense) dlist[base + excl + r] = key;
+        }
+    }
+    if (dense && tid == 0) *it.nsel = run;
+    __syncthreads();   // (device timing: thread 0 stamps the end after every wave's walk)
+}
+
 // k_fine_lanes: EvaluateHighResolutionMap (:227-256) for every selected block
 // of the batch, one wave per block and one LANE per fine pose (lr * lr <= 64
 // lanes): each lane walks the beams in order with pipelined gathers (seq_sum:
@@ -4492,6 +4624,14 @@ inline bool uses_super(const lgs_ctx* ctx, int nv_max, int nsb2, bool dense)
            nsb2 <= 64 && nsb2 >= ctx->prune_min_super;
 }
 
+// k_select_list replaces k_select + k_compact: a work-list batch (the caller
+// checks that it takes the list) whose largest K fits LGS_OPT_SELECT_LIST
+// and the kernel's LDS bitmap
+inline bool select_list_fits(const lgs_ctx* ctx, const BatchShape& B)
+{
+    return B.wl.cnt && (long long)B.Tmax * B.P <= std::min(ctx->select_list, kSelListMaxK);
+}
+
 // Per-item workspace: one contiguous region per item carved from S_BATCH_WS
 // (sized for the batch's largest plan), field offsets below.
 struct ItemLayout {
@@ -5156,6 +5296,7 @@ void enqueue_items(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::
         }
     }
     const bool dense = opt.dense || ctx->force_dense;
+    bool wl = false;   // the batch takes the kept-superblock work list
     if (B.pruned) {
         {
             const int tok = ctx->timing_begin(K_SUPER, 8.0 * B.nsb2 * beams_T);
@@ -5207,7 +5348,7 @@ void enqueue_items(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::
         }
         // the work list's passes are timed apart (K_COARSE_AUX): K_COARSE is the
         // kernel that makes every coarse lookup (its algorithmic bytes)
-        const bool wl = n >= ctx->lanes_min_batch && B.wl.cnt && !ctx->skipped(K_COARSE);
+        wl = n >= ctx->lanes_min_batch && B.wl.cnt && !ctx->skipped(K_COARSE);
         if (wl) {
             const int tk = ctx->timing_begin(K_COARSE_AUX, 8.0 * (double)B.Tmax * B.nsb2 * n);   // bound reads
             hipLaunchKernelGGL(k_keep, dim3(B.Tmax, n), dim3(64), 0, st, d_items, B.wl, ctx->dts(tk));
@@ -5252,9 +5393,17 @@ void enqueue_items(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::
         ctx->timing_end(tok);
         LGS_HIP_CHECK(hipGetLastError());
     }
+    // work-list batches whose keys fit the LDS bitmap select from the list
+    // (the host knows K: no device-side fallback)
+    const bool sel_list = wl && select_list_fits(ctx, B) && !ctx->skipped(K_SELECT);
     {
         const int tok_ = ctx->timing_begin(K_SELECT, 10.0 * (double)B.Tmax * B.P * n);
-        if (!ctx->skipped(K_SELECT)) {
+        if (ctx->skipped(K_SELECT)) {
+        } else if (sel_list) {
+            // the listed superblocks' blocks only, and k_compact's dense list with them
+            hipLaunchKernelGGL(k_select_list, dim3(n), dim3(kSelListThreads), sizeof(unsigned long long) * 16 * (size_t)B.nsegMax,
+                               st, d_items, B.wl, B.fine_lanes ? 1 : 0, ctx->dts(tok_));
+        } else {
             if (n >= ctx->lanes_min_batch)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select<256>), dim3((unsigned)B.nsegMax, n), dim3(256), 0, st,
                                    d_items, B.pruned ? 1 : 0, ctx->dts(tok_));
@@ -5266,7 +5415,7 @@ void enqueue_items(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::
         LGS_HIP_CHECK(hipGetLastError());
     }
     if (B.fine_lanes) {
-        hipLaunchKernelGGL(k_compact, dim3(n), dim3(256), pref_bytes(B.nsegMax), st, d_items);
+        if (!sel_list) hipLaunchKernelGGL(k_compact, dim3(n), dim3(256), pref_bytes(B.nsegMax), st, d_items);
         LGS_HIP_CHECK(hipGetLastError());
         const int tok_ = ctx->timing_begin(K_FINE, 0.0);
         if (ctx->skipped(K_FINE)) {
@@ -5721,6 +5870,18 @@ void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost
         d.buf[11] = dps ? dps->hv_out : nullptr;
         d.bytes[11] = dps ? dps->hv_out_bytes : 0;
         d.gen = ij.gen;
+        if (!B.small) {   // the selection (k_match_small makes none)
+            d.list = ij.list;
+            d.segcnt = ij.segcnt;
+            d.nseg = ij.nseg;
+            if (B.fine_lanes) {   // the dense list exists
+                d.nsel = ij.nsel;
+                d.dlist = ij.dlist;
+                d.K = (size_t)q.K;
+            }
+            d.sel_list = n >= ctx->lanes_min_batch && !ctx->skipped(K_COARSE) && !ctx->skipped(K_SELECT) &&
+                         select_list_fits(ctx, B);
+        }
     }
     const size_t items_off = up.append(items.data(), items.size());
     up.flush();
@@ -6090,10 +6251,32 @@ void cost_summaries(lgs_ctx* ctx, const lgs_grid* grid, const lgs_cost_ge_params
 
 extern "C" int lgs_debug_item_buffer(lgs_ctx* ctx, int item, int which, void* out, size_t cap, size_t* bytes)
 {
-    if (!ctx || which < 0 || which >= 12 || item < 0) return LGS_ERR_INVALID_ARG;
+    if (!ctx || which < 0 || which >= 16 || item < 0) return LGS_ERR_INVALID_ARG;
     return guarded(ctx, [&] {
         LGS_REQUIRE((size_t)item < ctx->dbg.size(), "no such item in the last correlative batch");
         const lgs_ctx::DbgItem& d = ctx->dbg[(size_t)item];
+        if (which >= 12) {   // the selection: two device buffers (14) or a host value (15)
+            const void* src[2] = { nullptr, nullptr };
+            size_t sz[2] = { 0, 0 };
+            const int sel = d.sel_list;
+            if (which == 12 && d.list) src[0] = d.list, sz[0] = sizeof(int) * (size_t)d.nseg * kSelSeg;
+            if (which == 13 && d.segcnt) src[0] = d.segcnt, sz[0] = sizeof(int) * (size_t)d.nseg;
+            if (which == 14 && d.nsel) src[0] = d.nsel, sz[0] = sizeof(int), src[1] = d.dlist, sz[1] = sizeof(int) * d.K;
+            if (which == 15) sz[0] = sizeof(int);
+            if (bytes) *bytes = sz[0] + sz[1];
+            if (!out || cap == 0) return;
+            LGS_HIP_CHECK(hipSetDevice(ctx->device));
+            ctx->sync();
+            size_t done = 0;
+            for (int i = 0; i < 2; ++i) {
+                const size_t k = std::min(cap - done, sz[i]);
+                if (!k) continue;
+                if (src[i]) LGS_HIP_CHECK(hipMemcpy((char*)out + done, src[i], k, hipMemcpyDeviceToHost));
+                else memcpy((char*)out + done, &sel, std::min(k, sizeof(int)));
+                done += k;
+            }
+            return;
+        }
         const size_t n = d.bytes[which];
         if (bytes) *bytes = n;
         if (!out || cap == 0) return;

@@ -562,6 +562,10 @@ extern "C" int lgs_ctx_set_option(lgs_ctx* ctx, int option, double value)
         if (!(value >= 0.0)) return LGS_ERR_INVALID_ARG;
         ctx->loop_group = (int)std::min(value, 134217728.0);
         return LGS_OK;
+    case LGS_OPT_SELECT_LIST:
+        if (!(value >= 0.0)) return LGS_ERR_INVALID_ARG;
+        ctx->select_list = (long long)std::min(value, 9.0e18);
+        return LGS_OK;
     case LGS_OPT_SEED_WIDE:
         if (!(value >= 0.0 && value <= 16.0)) return LGS_ERR_INVALID_ARG;
         ctx->seed_wide = (int)value;

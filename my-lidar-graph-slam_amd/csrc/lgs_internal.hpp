@@ -323,6 +323,21 @@ struct DtsScope {
     __device__ explicit DtsScope(const DevTs& x) : d(x) { dts_begin(d); }
     __device__ ~DtsScope() { dts_end(d); }
 };
+// The same for launches of a few workgroups that carry uneven work (one per
+// item: the last to finish may be any of them): every workgroup stamps its end.
+struct DtsScopeAll {
+    const DevTs d;
+    __device__ explicit DtsScopeAll(const DevTs& x) : d(x) { dts_begin(d); }
+    __device__ ~DtsScopeAll()
+    {
+        if (d.w && threadIdx.x == 0 && threadIdx.y == 0) {
+            const unsigned b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+            const unsigned long long t = __builtin_amdgcn_s_memrealtime() & kDtsMask;
+            __hip_atomic_fetch_max(d.w + 2 * (b & (unsigned)(kDtsSub - 1)) + 1, d.tag | t, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+};
 }  // namespace lgs
 
 struct lgs_ctx {
@@ -365,6 +380,7 @@ struct lgs_ctx {
     hipEvent_t split_ev[2] = {};
     bool post_records = true;    // records written to pinned memory by k_post + a flag (LGS_OPT_POST_RECORDS)
     long long copies_direct = 0, copies_staged = 0;   // lgs_debug_copy_counters
+    long long select_list = 524288;   // work-list batches of at most this many keys per item select from the list (k_select_list; LGS_OPT_SELECT_LIST, 0 = never)
     int lanes_min_batch = 2;     // pruned coarse stage: the work list (k_coarse_list) from this batch size on (LGS_OPT_LANES_MIN_BATCH)
     long long ray_chunk_keys = 1LL << 28;  // ray-cast keys per emit/sort/apply pass (LGS_OPT_RAY_CHUNK_KEYS)
     // Stamps come from one process-wide counter: a context's scratch may be
@@ -382,6 +398,10 @@ struct lgs_ctx {
         const void* buf[12];
         size_t bytes[12];
         int gen;
+        // the selection (which 12-15): list, segcnt, nsel + dlist (null: no dense list), and which kernel wrote them
+        const int *list, *segcnt, *nsel, *dlist;
+        int nseg, sel_list;
+        size_t K;
     };
     std::vector<DbgItem> dbg;
     int generation = 0;          // per-enqueue stamp (edge flags need no memset), from next_stamp()

@@ -58,6 +58,7 @@ KERNEL_IDS = ["k_project", "k_coarse", "k_seed", "k_select", "k_fine", "k_replay
 MORE_KERNEL_IDS = ["k_loop_search"]
 LGS_OPT_LOOP_SEARCH_MIN_PAIRS = 39  # lgs_loop_search_nearest: hint x position pairs below which the host loop runs (0: always the device)
 LGS_OPT_LOOP_SEARCH_GROUP = 40      # tests: walk positions per workgroup group of the search (0: chosen per call)
+LGS_OPT_SELECT_LIST = 41            # work-list batches: largest K selected from the kept-superblock list (k_select_list; 0: never)
 
 
 class Pose2D(C.Structure):
@@ -1273,7 +1274,10 @@ class Context:
     DEBUG_BUFFERS = {"sbound": (0, np.float64), "part_c": (1, np.float64), "part_k": (2, np.int64),
                      "L": (3, np.float64), "tedge": (4, np.int32), "cbase": (5, np.int32), "idx": (6, np.int32),
                      "cscore": (7, np.float64), "planes": (8, np.float64), "super": (9, np.float16),
-                     "hv_inmask": (10, np.uint64), "hv_outmask": (11, np.uint64)}
+                     "hv_inmask": (10, np.uint64), "hv_outmask": (11, np.uint64),
+                     # the selection: list [nseg, 1024], segcnt [nseg], [nsel, dlist...], [1 = k_select_list wrote it]
+                     "sel_list": (12, np.int32), "sel_segcnt": (13, np.int32), "sel_dense": (14, np.int32),
+                     "sel_by_list": (15, np.int32)}
 
     def debug_buffer(self, name: str, item: int = 0) -> np.ndarray:
         """Diagnostics: an intermediate buffer of one item of the last
