@@ -29,6 +29,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_loop_search
 	$(MAKE) -C tests/cpp_hv
 	$(MAKE) -C tests/cpp_loop
+	$(MAKE) -C tests/cpp_pg_cases
 
 clean:
 	$(MAKE) -C my-lidar-graph-slam_amd/csrc clean
@@ -48,5 +49,6 @@ clean:
 	$(MAKE) -C tests/cpp_loop_search clean
 	$(MAKE) -C tests/cpp_hv clean
 	$(MAKE) -C tests/cpp_loop clean
+	$(MAKE) -C tests/cpp_pg_cases clean
 
 .PHONY: all hip host oracle oracle_ref cpptest clean
