@@ -1166,6 +1166,95 @@ int  lgs_icp_ref_optimize_pose_batch(lgs_ctx* ctx, const lgs_icp_ref* const* ref
 int  lgs_icp_ref_pairs(lgs_ctx* ctx, const lgs_icp_ref* ref, const lgs_scan* scan, lgs_pose2d sensor_pose,
                        const lgs_icp_params* params, int* ref_index, int* beam_index, double* residual);
 
+/* ---- many ICP references in one pass, one per local map (k_icp_ref.hip) ----
+ * The graph snapshot is that of lgs_maps_construct_from_scans: scans[n_scans] at
+ * robot poses[n_scans] and n_refs inclusive node ranges idx_min[i] <= idx_max[i]
+ * < n_scans, which may overlap (a scan may belong to several references).
+ * Reference i of the set is, in everything a caller can observe,
+ *   lgs_icp_ref_create(scans[idx_min[i] .. idx_max[i]], poses[same], params):
+ * lgs_icp_ref_info, lgs_icp_ref_pairs (ref_index counted from the range's first
+ * scan) and lgs_icp_ref_optimize_pose / _batch (summary, trajectory, Hessian)
+ * give the same bytes; the order inside a grid cell stays free, as in 4.5c.  A
+ * range whose beams are all unusable gives an empty reference, legal as there.
+ * The build is one pass over the whole set: two device allocations (tables,
+ * cells) that every reference's arrays point into at 256-byte-aligned offsets,
+ * one launch of each of four kernels (table; count, scan, scatter of the
+ * grids) and two host waits on the stream, whatever n_refs is.
+ * lgs_icp_ref_set_ref(set, i) is borrowed: valid until the set is destroyed,
+ * ignored by lgs_icp_ref_destroy, accepted by every lgs_icp_ref_* refine-time
+ * call and free to share a batch with references lgs_icp_ref_create made; NULL
+ * for an index outside 0 .. size - 1.  Like an lgs_icp_ref the set copies what
+ * it needs and may be destroyed after its context.
+ * LGS_ERR_INVALID_ARG, before any device work: a NULL argument, n_refs < 1 or
+ * > 4096, a range outside [0, n_scans) or idx_min > idx_max, every
+ * per-reference rule of lgs_icp_ref_create (1 .. 4096 scans, at most
+ * LGS_ICP_REF_MAX_ENTRIES usable beams, finite poses, no NULL or empty scan,
+ * the parameter rules), more than LGS_ICP_REF_SET_MAX_ENTRIES usable beams over
+ * the whole set.  LGS_ERR_OOM, after the table pass (the grids are known only
+ * then): more than LGS_ICP_REF_SET_MAX_CELLS grid cells over the whole set;
+ * nothing leaks and the context stays usable.  An angle outside the restated
+ * sincos domain: LGS_ERR_INTERNAL.  A failing call writes nothing to *out. */
+#define LGS_ICP_REF_SET_MAX_ENTRIES 4194304   /* over the whole set */
+#define LGS_ICP_REF_SET_MAX_CELLS   16777216  /* grid cells over the whole set */
+typedef struct lgs_icp_ref_set lgs_icp_ref_set;
+int  lgs_icp_ref_set_create(lgs_ctx* ctx, const lgs_scan* const* scans, const lgs_pose2d* poses, int n_scans,
+                            const int* idx_min, const int* idx_max, int n_refs, const lgs_icp_params* params,
+                            lgs_icp_ref_set** out);
+void lgs_icp_ref_set_destroy(lgs_icp_ref_set* set);
+int  lgs_icp_ref_set_size(const lgs_icp_ref_set* set);   /* 0 for NULL */
+const lgs_icp_ref* lgs_icp_ref_set_ref(const lgs_icp_ref_set* set, int i);
+/* Counters of this context since its creation (each may be NULL): set builds
+ * that reached the device; launches of the build's table, count, scan and
+ * scatter kernels; host waits on the stream made by set builds; launches of
+ * the refine kernel by any lgs_icp_ref_optimize_pose / _batch or
+ * lgs_loop_refine_icp call. */
+int  lgs_icp_ref_set_stats(const lgs_ctx* ctx, long long* builds, long long* table_launches,
+                           long long* count_launches, long long* scan_launches, long long* scatter_launches,
+                           long long* build_syncs, long long* refine_launches);
+/* Diagnostics: the host clock of this context's last successful set build, in
+ * milliseconds (each may be NULL): from the call's first device work to the
+ * end of the wait behind the table pass (allocation, uploads, the table
+ * kernel, the boxes' download), and from there to the end of the build (the
+ * grids' geometry, allocation, count, scan, scatter, the final wait). */
+int  lgs_icp_ref_set_last_build_ms(const lgs_ctx* ctx, double* table_ms, double* grids_ms);
+
+/* ---- loop records refined by ICP against those references ----
+ * results[num_candidates] are a loop detector's records (in/out), queries and
+ * candidates the batch that made them; of a query only local_map_node_pose,
+ * first_candidate and num_candidates are read (map and coarse may be NULL), of
+ * a candidate only its scan.  refs[q] is query q's reference.  Every candidate
+ * c of query q with results[c].found != 0 and a finite results[c].estimated_pose
+ * becomes one item -- candidates[c].scan from that pose against refs[q] -- and
+ * all items run as one lgs_icp_ref_optimize_pose_batch (one launch per 4096
+ * items, one synchronisation; no item: no device work at all).
+ * The item is accepted iff, in fp64 without contraction on the host,
+ *   pose_found != 0, num_pairs >= min_pairs, normalized_cost <= max_normalized_cost,
+ *   dx * dx + dy * dy <= max_translation * max_translation   (refined estimate minus the record's),
+ *   fabs(NormalizeAngle(theta' - theta)) <= max_rotation      (H/util.hpp:125-135);
+ * a NaN fails every comparison.  An accepted record gets estimated_pose,
+ * covariance and normalized_cost of the item's summary and relative_pose =
+ * InverseCompound(queries[q].local_map_node_pose, estimated_pose); every other
+ * byte stays (found, the indices, start_node_pose, score, pad) and refined[c] =
+ * 1.  Every other record -- not found, estimate not finite, rejected -- keeps
+ * its 176 bytes and refined[c] = 0.  summaries (may be NULL; num_candidates
+ * entries) receives each item's summary, zero bytes for a candidate that did
+ * not run.
+ * LGS_ERR_INVALID_ARG, before any device work: a NULL argument (summaries
+ * apart; a NULL refs[q] or candidate scan included), num_queries or
+ * num_candidates < 0, queries that do not cover the candidates contiguously,
+ * in order and completely (the rule of lgs_loop_detect_rtcsm), min_pairs < 3, a
+ * gate value that is NaN or negative (+inf is legal), and for every item the
+ * refine-time rules of lgs_icp_ref_*.  A failing call leaves results, refined
+ * and summaries untouched. */
+typedef struct {
+    int    min_pairs;
+    double max_normalized_cost, max_translation, max_rotation;
+} lgs_loop_refine_gate;
+int  lgs_loop_refine_icp(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs_loop_query* queries, int num_queries,
+                         const lgs_loop_candidate* candidates, int num_candidates, const lgs_icp_params* params,
+                         const lgs_loop_refine_gate* gate, lgs_loop_result* results, int* refined,
+                         lgs_icp_summary* summaries);
+
 /* ---- nearest-node loop searcher (k_loop_search.hip) ----
  * LoopSearcherNearest::Search (C/mapping/loop_searcher_nearest.cpp:13-108) over
  * flat arrays, batched over hints.  A graph snapshot is poses[n] (node k has

@@ -23,9 +23,19 @@
 //                            order inside the cells does not matter and the
 //                            result is a function of the inputs alone.
 //   pairs   k_icp_ref_pairs  the search alone
+//
+// Many references in one pass (lgs_icp_ref_set_create): the
+// same table kernel over all (reference, scan) jobs, then
+//           k_icpref_count_set    k_icpref_count over a flat list of 256-entry
+//                                 blocks, none of which straddles two references
+//           k_icpref_scan_set     k_icpref_scan's body, one workgroup per reference
+//           k_icpref_scatter_set  k_icpref_scatter over the same block list
+// into two allocations that every reference's IcpRefDev points into.
 #include "icp_device.hpp"
 #include "icp_ref_host.hpp"
+#include "icp_ref_set_host.hpp"
 
+#include <chrono>
 #include <memory>
 #include <vector>
 
@@ -53,11 +63,19 @@ struct IcpRefDev {
 struct lgs_icp_ref {
     lgs_ctx* ctx = nullptr;   // creating context (compared, never used after its destruction)
     int device = 0;
+    bool borrowed = false;    // a member of an lgs_icp_ref_set: the set owns the memory, destroy is a no-op
     IcpRefBound bound{};
     int n_refs = 0, entries = 0, lines = 0;
     void* mem_table = nullptr;   // tq, tn, tkj
     void* mem_cells = nullptr;   // cq, cidx, starts
     IcpRefDev dev{};
+};
+
+struct lgs_icp_ref_set {
+    int device = 0;
+    void* mem_table = nullptr;   // every reference's tq, tn, tkj
+    void* mem_cells = nullptr;   // every reference's cq, cidx, starts
+    std::vector<lgs_icp_ref> refs;   // borrowed views into the two
 };
 
 namespace {
@@ -69,12 +87,10 @@ struct RefScanJob {
     double lo, hi;
     int n;
     int base, count;   // the scan's first entry and its usable beams (host count)
+    int label, pad;    // the scan's index within its own reference (tkj.x)
 };
 
-struct RefScanBox {
-    double min_x, max_x, min_y, max_y;   // over finite points; min > max: none
-    int lines, pad;
-};
+using RefScanBox = IcpRefScanBox;
 
 struct IcpRefItem {
     IcpItem it;        // the current scan's half (r_* unused)
@@ -116,7 +132,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_icpref_table(const RefScanJob* 
             const int e = job.base + off;
             tq[e] = make_double2(qx, qy);
             tn[e] = make_double2(nx, ny);
-            tkj[e] = make_int2((int)blockIdx.x, j);
+            tkj[e] = make_int2(job.label, j);
             if (qx - qx == 0.0 && qy - qy == 0.0) {
                 mnx = fmin(mnx, qx);
                 mxx = fmax(mxx, qx);
@@ -182,10 +198,9 @@ __global__ __launch_bounds__(256) void k_icpref_count(const double2* __restrict_
 
 // starts[c] = sum of counts[< c], starts[ncell] = the total; one workgroup,
 // thread t owns the cells [t * chunk, (t + 1) * chunk)
-__global__ __launch_bounds__(kIcpThreads) void k_icpref_scan(const int* __restrict__ counts, int ncell,
-                                                             int* __restrict__ starts)
+__device__ __forceinline__ void icpref_scan_body(const int* __restrict__ counts, int ncell, int* __restrict__ starts,
+                                                 int* part)
 {
-    __shared__ int part[kIcpThreads];
     const int t = threadIdx.x;
     const int chunk = (ncell + kIcpThreads - 1) / kIcpThreads;
     const int c0 = min(ncell, t * chunk), c1 = min(ncell, c0 + chunk);
@@ -207,6 +222,13 @@ __global__ __launch_bounds__(kIcpThreads) void k_icpref_scan(const int* __restri
     if (t == kIcpThreads - 1) starts[ncell] = part[t];
 }
 
+__global__ __launch_bounds__(kIcpThreads) void k_icpref_scan(const int* __restrict__ counts, int ncell,
+                                                             int* __restrict__ starts)
+{
+    __shared__ int part[kIcpThreads];
+    icpref_scan_body(counts, ncell, starts, part);
+}
+
 // consumes counts (each cell's falls to 0)
 __global__ __launch_bounds__(256) void k_icpref_scatter(const double2* __restrict__ tq, int m, IcpRefGrid g,
                                                         const int* __restrict__ starts, int* __restrict__ counts,
@@ -221,6 +243,58 @@ __global__ __launch_bounds__(256) void k_icpref_scatter(const double2* __restric
     if (p < 0 || p >= m) return;
     cq[p] = q;
     cidx[p] = e;
+}
+
+// ---- the set's grids: reference i's entries from ebase on in the table and
+// cell-order arrays, its counts and starts from cbase on; m entries, ncell cells
+struct IcpRefSeg {
+    IcpRefGrid g;
+    int ebase, cbase, m, ncell;
+};
+
+__global__ __launch_bounds__(kIcpRefSetBlock) void k_icpref_count_set(const IcpRefSetBlock* __restrict__ blocks,
+                                                                     const IcpRefSeg* __restrict__ segs,
+                                                                     const double2* __restrict__ tq,
+                                                                     int* __restrict__ counts)
+{
+    const IcpRefSetBlock b = blocks[blockIdx.x];
+    if ((int)threadIdx.x >= b.count) return;
+    const IcpRefSeg s = segs[b.ref];
+    const int e = b.first + (int)threadIdx.x;
+    if (e >= s.m) return;
+    const int c = icpref_cell_of(s.g, tq[s.ebase + e]);
+    if (c >= 0) atomicAdd(counts + s.cbase + c, 1);
+}
+
+__global__ __launch_bounds__(kIcpThreads) void k_icpref_scan_set(const IcpRefSeg* __restrict__ segs,
+                                                                 const int* __restrict__ counts,
+                                                                 int* __restrict__ starts)
+{
+    __shared__ int part[kIcpThreads];
+    const IcpRefSeg s = segs[blockIdx.x];
+    icpref_scan_body(counts + s.cbase, s.ncell, starts + s.cbase, part);
+}
+
+// consumes counts; cell indices and cidx are local to the reference
+__global__ __launch_bounds__(kIcpRefSetBlock) void k_icpref_scatter_set(const IcpRefSetBlock* __restrict__ blocks,
+                                                                       const IcpRefSeg* __restrict__ segs,
+                                                                       const double2* __restrict__ tq,
+                                                                       const int* __restrict__ starts,
+                                                                       int* __restrict__ counts,
+                                                                       double2* __restrict__ cq, int* __restrict__ cidx)
+{
+    const IcpRefSetBlock b = blocks[blockIdx.x];
+    if ((int)threadIdx.x >= b.count) return;
+    const IcpRefSeg s = segs[b.ref];
+    const int e = b.first + (int)threadIdx.x;
+    if (e >= s.m) return;
+    const double2 q = tq[s.ebase + e];
+    const int c = icpref_cell_of(s.g, q);
+    if (c < 0) return;
+    const int p = starts[s.cbase + c] + atomicSub(counts + s.cbase + c, 1) - 1;
+    if (p < 0 || p >= s.m) return;
+    cq[s.ebase + p] = q;
+    cidx[s.ebase + p] = e;
 }
 
 // the lexicographic minimum of (d2, index) over the cells a hit point visits;
@@ -308,7 +382,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_icp_ref_pairs(IcpRefItem X, Icp
 // ------------------------------------------------------------------ host
 void icp_ref_free(lgs_icp_ref* r)
 {
-    if (!r) return;
+    if (!r || r->borrowed) return;
     // hipFree synchronises with the device; the creating context may already
     // be gone, so it is not touched here
     if (r->mem_table || r->mem_cells) {
@@ -346,6 +420,7 @@ lgs_icp_ref* ref_create(lgs_ctx* ctx, const lgs_scan* const* scans, const lgs_po
         j.lo = std::max(p->usable_range_min, scans[k]->min_range);
         j.hi = std::min(p->usable_range_max, scans[k]->max_range);
         j.n = scans[k]->n;
+        j.label = k;
         usable[(size_t)k] = icp_usable_count(scans[k]->h_ranges.data(), scans[k]->n, j.lo, j.hi);
     }
     LGS_REQUIRE(icp_ref_counts_check(K, usable.data()) == LGS_OK,
@@ -493,6 +568,7 @@ void run_icp_ref(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs_scan* c
         hipLaunchKernelGGL(k_icp_ref, dim3(m), dim3(kIcpThreads), 0, ctx->stream, up.at<IcpRefItem>(io) + j0, sh,
                            d_rec + j0, d_err);
         LGS_HIP_CHECK(hipGetLastError());
+        ctx->icpref_refine_launches += 1;
     }
     char* pin = (char*)ctx->ensure_pinned(hb);
     LGS_HIP_CHECK(hipMemcpyAsync(pin, small, hb, hipMemcpyDeviceToHost, ctx->stream));
@@ -504,7 +580,279 @@ void run_icp_ref(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs_scan* c
     if (traj) std::memcpy(traj, pin + rb, sizeof(double) * 5 * (size_t)out[0].iterations);
 }
 
+// ------------------------------------------------------------------ the set
+void icp_ref_set_free(lgs_icp_ref_set* s)
+{
+    if (!s) return;
+    if (s->mem_table || s->mem_cells) {
+        hipSetDevice(s->device);
+        if (s->mem_table) hipFree(s->mem_table);
+        if (s->mem_cells) hipFree(s->mem_cells);
+    }
+    delete s;
+}
+
+struct RefSetDeleter {
+    void operator()(lgs_icp_ref_set* s) const { icp_ref_set_free(s); }
+};
+
+lgs_icp_ref_set* ref_set_create(lgs_ctx* ctx, const lgs_scan* const* scans, const lgs_pose2d* poses, int n_scans,
+                                const int* idx_min, const int* idx_max, int n_refs, const lgs_icp_params* p)
+{
+    // every check before any device work
+    LGS_REQUIRE(icp_ref_set_ranges_check(n_scans, idx_min, idx_max, n_refs) == LGS_OK,
+                "icp ref set: 1 .. 4096 ranges of 1 .. 4096 scans inside [0, n_scans), idx_min <= idx_max");
+    // per scan of some range: the job's scan half and the usable beams
+    std::vector<char> in_range((size_t)n_scans, 0);
+    for (int i = 0; i < n_refs; ++i)
+        for (int k = idx_min[i]; k <= idx_max[i]; ++k) in_range[(size_t)k] = 1;
+    std::vector<RefScanJob> of_scan((size_t)n_scans);
+    std::vector<int> usable((size_t)n_scans, 0);
+    std::vector<const lgs_scan*> used;
+    for (int k = 0; k < n_scans; ++k) {
+        if (!in_range[(size_t)k]) continue;
+        LGS_REQUIRE(scans[k], "icp ref set: null scan");
+        LGS_REQUIRE(scans[k]->n >= 1, "icp ref set: empty scan");
+        LGS_REQUIRE(icp_pose_finite(poses[k]), "icp ref set: pose not finite");
+        const lgs_pose2d sp = compound(poses[k], scans[k]->rel);
+        LGS_REQUIRE(icp_pose_finite(sp), "icp ref set: pose not finite");
+        RefScanJob& j = of_scan[(size_t)k];
+        std::memset(&j, 0, sizeof(j));
+        j.pose[0] = sp.x;
+        j.pose[1] = sp.y;
+        j.pose[2] = sp.theta;
+        j.lo = std::max(p->usable_range_min, scans[k]->min_range);
+        j.hi = std::min(p->usable_range_max, scans[k]->max_range);
+        j.n = scans[k]->n;
+        usable[(size_t)k] = icp_usable_count(scans[k]->h_ranges.data(), scans[k]->n, j.lo, j.hi);
+        used.push_back(scans[k]);
+    }
+    IcpRefSetLayout L;
+    LGS_REQUIRE(icp_ref_set_layout(usable.data(), idx_min, idx_max, n_refs, L) == LGS_OK,
+                "icp ref set: more than LGS_ICP_REF_MAX_ENTRIES usable beams in a reference or "
+                "LGS_ICP_REF_SET_MAX_ENTRIES in the set");
+    // the jobs, reference by reference; a scan without a usable beam writes no
+    // entry, has no box and no line and forms no angle, so it needs no job
+    std::vector<RefScanJob> jobs;
+    std::vector<int> job_ref;
+    for (int i = 0; i < n_refs; ++i) {
+        int at = L.entry_base[(size_t)i];
+        for (int k = idx_min[i]; k <= idx_max[i]; ++k) {
+            if (usable[(size_t)k] == 0) continue;
+            RefScanJob j = of_scan[(size_t)k];
+            j.label = k - idx_min[i];
+            j.base = at;
+            j.count = usable[(size_t)k];
+            at += j.count;
+            jobs.push_back(j);
+            job_ref.push_back(i);
+        }
+    }
+
+    const auto t0 = std::chrono::steady_clock::now();
+    LGS_HIP_CHECK(hipSetDevice(ctx->device));
+    std::unique_ptr<lgs_icp_ref_set, RefSetDeleter> set(new lgs_icp_ref_set());
+    set->device = ctx->device;
+    set->refs.resize((size_t)n_refs);
+    const size_t T = (size_t)L.entry_total;
+    const size_t qb = sizeof(double2) * T, kb = sizeof(int2) * T, ib = sizeof(int) * T;   // multiples of 256
+    if (hipMalloc(&set->mem_table, 2 * qb + kb) != hipSuccess)
+        throw Error(LGS_ERR_OOM, "hipMalloc failed for icp ref set");
+    double2* tq = (double2*)set->mem_table;
+    double2* tn = (double2*)((char*)set->mem_table + qb);
+    int2* tkj = (int2*)((char*)set->mem_table + 2 * qb);
+    // (the slots between references are never read: defined bytes all the same)
+    LGS_HIP_CHECK(hipMemsetAsync(set->mem_table, 0, 2 * qb + kb, ctx->stream));
+    if (!jobs.empty()) ctx->icpset_builds += 1;
+
+    // the table, the boxes: one launch, one wait
+    std::vector<IcpRefSetBox> boxes((size_t)n_refs);
+    if (!jobs.empty()) {
+        scans_to_device(ctx, used.data(), (int)used.size());
+        for (size_t j = 0; j < jobs.size(); ++j) {
+            const int k = idx_min[job_ref[j]] + jobs[j].label;   // the scan the job was made from
+            jobs[j].ranges = scans[k]->d_ranges;
+            jobs[j].angles = scans[k]->d_angles;
+        }
+        const size_t bb = icp_align256(sizeof(RefScanBox) * jobs.size());
+        char* small = (char*)ctx->ensure(S_ICP0, bb + 256);
+        int* d_err = (int*)(small + bb);
+        LGS_HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
+        Upload up(ctx);
+        const size_t jo = up.append(jobs.data(), jobs.size());
+        up.flush();
+        hipLaunchKernelGGL(k_icpref_table, dim3((unsigned)jobs.size()), dim3(kIcpThreads), 0, ctx->stream,
+                           up.at<RefScanJob>(jo), p->max_segment_length * p->max_segment_length, tq, tn, tkj,
+                           (RefScanBox*)small, d_err);
+        LGS_HIP_CHECK(hipGetLastError());
+        ctx->icpset_launches[0] += 1;
+        char* pin = (char*)ctx->ensure_pinned(bb + 256);
+        LGS_HIP_CHECK(hipMemcpyAsync(pin, small, bb + 256, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        ctx->icpset_syncs += 1;
+        if (*(const int*)(pin + bb) != 0) throw Error(LGS_ERR_INTERNAL, kSincosMsg);
+        boxes = icp_ref_set_boxes((const RefScanBox*)pin, job_ref.data(), jobs.size(), n_refs);
+    }
+
+    const auto t1 = std::chrono::steady_clock::now();
+
+    // the grids
+    std::vector<IcpRefGrid> grids((size_t)n_refs);
+    for (int i = 0; i < n_refs; ++i) {
+        const double* bx = boxes[(size_t)i].bx;
+        grids[(size_t)i] = icp_ref_geometry(bx[0], bx[1], bx[2], bx[3], p->max_correspondence_dist);
+    }
+    IcpRefSetCells Cl;
+    if (icp_ref_set_cells(grids, Cl) != LGS_OK)
+        throw Error(LGS_ERR_OOM, "icp ref set: more than LGS_ICP_REF_SET_MAX_CELLS grid cells over the set");
+    const size_t sb = sizeof(int) * (size_t)Cl.segment_total;
+    if (hipMalloc(&set->mem_cells, qb + ib + sb) != hipSuccess)
+        throw Error(LGS_ERR_OOM, "hipMalloc failed for icp ref set");
+    double2* cq = (double2*)set->mem_cells;
+    int* cidx = (int*)((char*)set->mem_cells + qb);
+    int* starts = (int*)((char*)set->mem_cells + qb + ib);
+    LGS_HIP_CHECK(hipMemsetAsync(set->mem_cells, 0, qb + ib + sb, ctx->stream));
+    if (!jobs.empty()) {
+        std::vector<IcpRefSeg> segs((size_t)n_refs);
+        for (int i = 0; i < n_refs; ++i)
+            segs[(size_t)i] = IcpRefSeg{ grids[(size_t)i], L.entry_base[(size_t)i], Cl.cell_base[(size_t)i],
+                                         L.entries[(size_t)i], Cl.cells[(size_t)i] };
+        const std::vector<IcpRefSetBlock> blocks = icp_ref_set_blocks(L.entries);
+        int* counts = (int*)ctx->ensure(S_ICPR0, sb);
+        LGS_HIP_CHECK(hipMemsetAsync(counts, 0, sb, ctx->stream));
+        Upload up(ctx);
+        const size_t so = up.append(segs.data(), segs.size());
+        const size_t bo = up.append(blocks.data(), blocks.size());
+        up.flush();
+        const IcpRefSeg* d_segs = up.at<IcpRefSeg>(so);
+        const IcpRefSetBlock* d_blocks = up.at<IcpRefSetBlock>(bo);
+        const dim3 bg((unsigned)blocks.size());
+        hipLaunchKernelGGL(k_icpref_count_set, bg, dim3(kIcpRefSetBlock), 0, ctx->stream, d_blocks, d_segs, tq, counts);
+        LGS_HIP_CHECK(hipGetLastError());
+        ctx->icpset_launches[1] += 1;
+        hipLaunchKernelGGL(k_icpref_scan_set, dim3((unsigned)n_refs), dim3(kIcpThreads), 0, ctx->stream, d_segs, counts,
+                           starts);
+        LGS_HIP_CHECK(hipGetLastError());
+        ctx->icpset_launches[2] += 1;
+        hipLaunchKernelGGL(k_icpref_scatter_set, bg, dim3(kIcpRefSetBlock), 0, ctx->stream, d_blocks, d_segs, tq, starts,
+                           counts, cq, cidx);
+        LGS_HIP_CHECK(hipGetLastError());
+        ctx->icpset_launches[3] += 1;
+    }
+    ctx->sync();
+    ctx->icpset_syncs += 1;
+    ctx->icpset_last_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    ctx->icpset_last_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    for (int i = 0; i < n_refs; ++i) {
+        lgs_icp_ref& r = set->refs[(size_t)i];
+        const int eb = L.entry_base[(size_t)i], cb = Cl.cell_base[(size_t)i];
+        r.ctx = ctx;
+        r.device = ctx->device;
+        r.borrowed = true;
+        r.bound = icp_ref_bound(p);
+        r.n_refs = idx_max[i] - idx_min[i] + 1;
+        r.entries = L.entries[(size_t)i];
+        r.lines = boxes[(size_t)i].lines;
+        r.dev = IcpRefDev{ tq + eb, tn + eb, tkj + eb, cq + eb, cidx + eb, starts + cb, grids[(size_t)i], r.entries };
+    }
+    return set.release();
+}
+
+// lgs_loop_refine_icp: results, refined and summaries are written only when the whole call succeeded
+void loop_refine_icp(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs_loop_query* queries, int num_queries,
+                     const lgs_loop_candidate* candidates, int num_candidates, const lgs_icp_params* p,
+                     const lgs_loop_refine_gate* gate, lgs_loop_result* results, int* refined,
+                     lgs_icp_summary* summaries)
+{
+    // every check before any device work
+    std::vector<int> query_of;
+    LGS_REQUIRE(loop_refine_ranges_check(queries, num_queries, num_candidates, query_of) == LGS_OK,
+                "loop queries must cover the candidates contiguously, in order and completely");
+    for (int q = 0; q < num_queries; ++q) LGS_REQUIRE(refs[q], "loop refine: a query without a reference");
+    std::vector<int> item_of;
+    std::vector<const lgs_icp_ref*> irefs;
+    std::vector<const lgs_scan*> iscans;
+    std::vector<lgs_pose2d> init;
+    for (int c = 0; c < num_candidates; ++c) {
+        LGS_REQUIRE(candidates[c].scan, "loop candidate without a scan");
+        if (!loop_refine_runs(results[c])) continue;
+        item_of.push_back(c);
+        irefs.push_back(refs[query_of[(size_t)c]]);
+        iscans.push_back(candidates[c].scan);
+        init.push_back(results[c].estimated_pose);
+    }
+    std::vector<lgs_icp_summary> sums(item_of.size());
+    if (!item_of.empty())
+        run_icp_ref(ctx, irefs.data(), iscans.data(), init.data(), (int)item_of.size(), p, sums.data(), nullptr);
+    // nothing can fail from here on
+    for (int c = 0; c < num_candidates; ++c) refined[c] = 0;
+    if (summaries && num_candidates > 0) std::memset(summaries, 0, sizeof(lgs_icp_summary) * (size_t)num_candidates);
+    for (size_t k = 0; k < item_of.size(); ++k) {
+        const int c = item_of[k];
+        if (summaries) summaries[c] = sums[k];
+        if (!loop_refine_accept(*gate, sums[k], results[c].estimated_pose)) continue;
+        loop_refine_update(results[c], queries[query_of[(size_t)c]].local_map_node_pose, sums[k]);
+        refined[c] = 1;
+    }
+}
+
 }  // namespace
+
+extern "C" int lgs_icp_ref_set_create(lgs_ctx* ctx, const lgs_scan* const* scans, const lgs_pose2d* poses, int n_scans,
+                                      const int* idx_min, const int* idx_max, int n_refs, const lgs_icp_params* params,
+                                      lgs_icp_ref_set** out)
+{
+    if (!ctx || !scans || !poses || !idx_min || !idx_max || !params || !out) return LGS_ERR_INVALID_ARG;
+    if (icp_params_check(params) != LGS_OK) return LGS_ERR_INVALID_ARG;
+    return guarded(ctx, [&] { *out = ref_set_create(ctx, scans, poses, n_scans, idx_min, idx_max, n_refs, params); });
+}
+
+extern "C" void lgs_icp_ref_set_destroy(lgs_icp_ref_set* set) { icp_ref_set_free(set); }
+
+extern "C" int lgs_icp_ref_set_size(const lgs_icp_ref_set* set) { return set ? (int)set->refs.size() : 0; }
+
+extern "C" const lgs_icp_ref* lgs_icp_ref_set_ref(const lgs_icp_ref_set* set, int i)
+{
+    if (!set || i < 0 || i >= (int)set->refs.size()) return nullptr;
+    return &set->refs[(size_t)i];
+}
+
+extern "C" int lgs_icp_ref_set_stats(const lgs_ctx* ctx, long long* builds, long long* table_launches,
+                                     long long* count_launches, long long* scan_launches, long long* scatter_launches,
+                                     long long* build_syncs, long long* refine_launches)
+{
+    if (!ctx) return LGS_ERR_INVALID_ARG;
+    if (builds) *builds = ctx->icpset_builds;
+    if (table_launches) *table_launches = ctx->icpset_launches[0];
+    if (count_launches) *count_launches = ctx->icpset_launches[1];
+    if (scan_launches) *scan_launches = ctx->icpset_launches[2];
+    if (scatter_launches) *scatter_launches = ctx->icpset_launches[3];
+    if (build_syncs) *build_syncs = ctx->icpset_syncs;
+    if (refine_launches) *refine_launches = ctx->icpref_refine_launches;
+    return LGS_OK;
+}
+
+extern "C" int lgs_icp_ref_set_last_build_ms(const lgs_ctx* ctx, double* table_ms, double* grids_ms)
+{
+    if (!ctx) return LGS_ERR_INVALID_ARG;
+    if (table_ms) *table_ms = ctx->icpset_last_ms[0];
+    if (grids_ms) *grids_ms = ctx->icpset_last_ms[1];
+    return LGS_OK;
+}
+
+extern "C" int lgs_loop_refine_icp(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs_loop_query* queries,
+                                   int num_queries, const lgs_loop_candidate* candidates, int num_candidates,
+                                   const lgs_icp_params* params, const lgs_loop_refine_gate* gate,
+                                   lgs_loop_result* results, int* refined, lgs_icp_summary* summaries)
+{
+    if (!ctx || !refs || !queries || !candidates || !params || !gate || !results || !refined)
+        return LGS_ERR_INVALID_ARG;
+    if (icp_params_check(params) != LGS_OK || loop_refine_gate_check(gate) != LGS_OK) return LGS_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        loop_refine_icp(ctx, refs, queries, num_queries, candidates, num_candidates, params, gate, results, refined,
+                        summaries);
+    });
+}
 
 extern "C" int lgs_icp_ref_create(lgs_ctx* ctx, const lgs_scan* const* ref_scans, const lgs_pose2d* ref_poses,
                                   int n_refs, const lgs_icp_params* params, lgs_icp_ref** out)

@@ -469,6 +469,11 @@ struct lgs_ctx {
     long long loop_device_calls = 0, loop_host_calls = 0, loop_launches = 0, loop_pairs = 0;
     // lgs_pg_lm_optimize (k_pglm.hip): the counters of lgs_pg_lm_stats
     long long pglm_optimizes = 0, pglm_steps = 0, pglm_pose_uploads = 0, pglm_pose_downloads = 0, pglm_incidence_builds = 0;
+    // lgs_icp_ref_set_create / lgs_loop_refine_icp (k_icp_ref.hip): the counters of lgs_icp_ref_set_stats
+    // (set builds that reached the device, launches of the four build kernels, host waits of the builds,
+    // launches of k_icp_ref by any lgs_icp_ref_* refine)
+    long long icpset_builds = 0, icpset_launches[4] = {}, icpset_syncs = 0, icpref_refine_launches = 0;
+    double icpset_last_ms[2] = {};   // the last build's host clock: up to the first wait (table), from there on (grids)
     // padded phase-plane buffer (per bank): margins zeroed once per (buffer, layout, set count)
     void* planes_ptr[2] = {};
     int planes_sets[2] = {};

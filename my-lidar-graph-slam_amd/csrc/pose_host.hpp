@@ -2,6 +2,8 @@
 // of the HIP runtime so that plain host programs can include it.
 #pragma once
 
+#include <cmath>
+
 #include "lgs_hip.h"
 
 extern "C" void sincos(double x, double* s, double* c);  // glibc
@@ -35,6 +37,17 @@ inline lgs_pose2d inverse_compound(lgs_pose2d s, lgs_pose2d e)
     ref_sincos(s.theta, sinT, cosT);
     const double dx = e.x - s.x, dy = e.y - s.y;
     return { cosT * dx + sinT * dy, -sinT * dx + cosT * dy, e.theta - s.theta };
+}
+// NormalizeAngle (H/util.hpp:125-135): the C library's fmod, then one turn
+inline double normalize_angle(double theta)
+{
+    const double pi = 3.14159265358979323846;   // M_PI
+    double t = ::fmod(theta, 2.0 * pi);
+    if (t > pi)
+        t -= 2.0 * pi;
+    else if (t < -pi)
+        t += 2.0 * pi;
+    return t;
 }
 
 }  // namespace lgs

@@ -788,6 +788,111 @@ void LoopDetectorGridSearchHip::Detect(std::vector<LoopDetectionQuery>& queries,
     });
 }
 
+// -------------------------------------------------------- IcpReferenceSetHip
+IcpReferenceSetHip::IcpReferenceSetHip(DevicePtr dev, const IcpPointToLineParams& p,
+                                       const std::vector<ScanDataPtr>& scans,
+                                       const std::vector<RobotPose2D<double>>& robotPoses,
+                                       const std::vector<int>& nodeIdxMin, const std::vector<int>& nodeIdxMax)
+    : mDev(std::move(dev))
+{
+    mParams = { p.mNumOfIterationsMax, p.mConvergenceThreshold, p.mUsableRangeMin, p.mUsableRangeMax,
+                p.mTranslationRegularizer, p.mRotationRegularizer, p.mMaxCorrespondenceDist, p.mMaxSegmentLength };
+    if (scans.empty() || scans.size() != robotPoses.size())
+        throw Error(LGS_ERR_INVALID_ARG, "IcpReferenceSetHip: need as many poses as scans, at least one");
+    if (nodeIdxMin.empty() || nodeIdxMin.size() != nodeIdxMax.size())
+        throw Error(LGS_ERR_INVALID_ARG, "IcpReferenceSetHip: need as many range ends as range starts, at least one");
+    std::vector<const lgs_scan*> hs;
+    std::vector<lgs_pose2d> poses;
+    for (std::size_t k = 0; k < scans.size(); ++k) {
+        hs.push_back(scans[k] ? scans[k]->Handle() : nullptr);   // a scan outside every range may be missing
+        poses.push_back(to_c(robotPoses[k]));
+    }
+    mDev->Check(lgs_icp_ref_set_create(mDev->Handle(), hs.data(), poses.data(), (int)hs.size(), nodeIdxMin.data(),
+                                       nodeIdxMax.data(), (int)nodeIdxMin.size(), &mParams, &mSet),
+                "lgs_icp_ref_set_create");
+}
+
+IcpReferenceSetHip::~IcpReferenceSetHip()
+{
+    if (mSet) lgs_icp_ref_set_destroy(mSet);
+}
+
+// --------------------------------------------------------- LoopRefinerIcpHip
+LoopRefinerIcpHip::LoopRefinerIcpHip(const LoopRefineGate& g)
+{
+    mGate = { g.mMinPairs, g.mMaxNormalizedCost, g.mMaxTranslation, g.mMaxRotation };
+}
+
+std::vector<int> LoopRefinerIcpHip::Refine(const IcpReferenceSetHip& set, const std::vector<int>& mapIndexOfQuery,
+                                           const std::vector<LoopDetectionQuery>& queries,
+                                           std::vector<LoopDetectionResult>& results)
+{
+    if (mapIndexOfQuery.size() != queries.size())
+        throw Error(LGS_ERR_INVALID_ARG, "LoopRefinerIcpHip: need one map index per query");
+    std::vector<const lgs_icp_ref*> refs;
+    std::vector<lgs_loop_query> qs;
+    std::vector<lgs_loop_candidate> cs;
+    std::vector<lgs_loop_result> recs;
+    std::vector<std::size_t> result_of;   // per candidate: its result, or results.size()
+    std::size_t next = 0;
+    for (std::size_t q = 0; q < queries.size(); ++q) {
+        const LoopDetectionQuery& Q = queries[q];
+        const lgs_icp_ref* ref = set.Reference(mapIndexOfQuery[q]);
+        if (!ref) throw Error(LGS_ERR_INVALID_ARG, "LoopRefinerIcpHip: map index outside the reference set");
+        refs.push_back(ref);
+        lgs_loop_query c{};
+        c.local_map_node_pose = to_c(Q.mLocalMapNodePose);
+        c.local_map_node_index = Q.mLocalMapNodeIndex;
+        c.first_candidate = (int)cs.size();
+        c.num_candidates = (int)Q.mPoseGraphNodes.size();
+        qs.push_back(c);
+        for (const auto& n : Q.mPoseGraphNodes) {
+            if (!n.mScanData) throw Error(LGS_ERR_INVALID_ARG, "LoopRefinerIcpHip: null scan");
+            cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
+            lgs_loop_result r{};
+            r.start_node_index = Q.mLocalMapNodeIndex;
+            r.end_node_index = n.mIndex;
+            std::size_t k = results.size();
+            if (next < results.size() && results[next].mStartNodeIdx == Q.mLocalMapNodeIndex &&
+                results[next].mEndNodeIdx == n.mIndex) {
+                k = next++;
+                const LoopDetectionResult& R = results[k];
+                r.found = 1;
+                r.relative_pose = to_c(R.mRelativePose);
+                r.start_node_pose = to_c(R.mStartNodePose);
+                // Compound(localMapNode.Pose(), relativePose), glibc's sincos as everywhere on the host
+                double sinT, cosT;
+                sincos(Q.mLocalMapNodePose.mTheta, &sinT, &cosT);
+                r.estimated_pose = { cosT * R.mRelativePose.mX - sinT * R.mRelativePose.mY + Q.mLocalMapNodePose.mX,
+                                     sinT * R.mRelativePose.mX + cosT * R.mRelativePose.mY + Q.mLocalMapNodePose.mY,
+                                     Q.mLocalMapNodePose.mTheta + R.mRelativePose.mTheta };
+                for (int i = 0; i < 9; ++i) r.covariance[i] = R.mEstimatedCovMat.m[i];
+            }
+            recs.push_back(r);
+            result_of.push_back(k);
+        }
+    }
+    if (next != results.size())
+        throw Error(LGS_ERR_INVALID_ARG, "LoopRefinerIcpHip: the results are not those of these queries, in order");
+    std::vector<int> refined(cs.size(), 0), flags(results.size(), 0);
+    std::vector<lgs_icp_summary> sums(cs.size());
+    mLast.assign(results.size(), lgs_icp_summary{});
+    if (results.empty()) return flags;
+    set.Dev()->Check(lgs_loop_refine_icp(set.Dev()->Handle(), refs.data(), qs.data(), (int)qs.size(), cs.data(),
+                                         (int)cs.size(), &set.Params(), &mGate, recs.data(), refined.data(), sums.data()),
+                     "lgs_loop_refine_icp");
+    for (std::size_t c = 0; c < cs.size(); ++c) {
+        const std::size_t k = result_of[c];
+        if (k == results.size()) continue;
+        mLast[k] = sums[c];
+        flags[k] = refined[c];
+        if (!refined[c]) continue;
+        results[k].mRelativePose = from_c(recs[c].relative_pose);
+        results[k].mEstimatedCovMat = cov_of(recs[c].covariance);
+    }
+    return flags;
+}
+
 // ---------------------------------------------------- LoopSearcherNearestHip
 namespace {
 

@@ -37,6 +37,7 @@
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -515,6 +516,64 @@ private:
     std::shared_ptr<ScanMatcherRealTimeCorrelativeHip> mScanMatcher;
     double mScoreThreshold;
     std::vector<DevicePtr> mExtraDevices;
+};
+
+// One ICP reference per local map (lgs_icp_ref_set_*): map i
+// is built from the pose-graph nodes nodeIdxMin[i]..nodeIdxMax[i] of (scans,
+// robotPoses), the ranges of GridMapHip::ConstructMapsFromScans, all maps in
+// one device pass.  The scans are not kept.
+class IcpReferenceSetHip {
+public:
+    IcpReferenceSetHip(DevicePtr dev, const IcpPointToLineParams& params, const std::vector<ScanDataPtr>& scans,
+                       const std::vector<RobotPose2D<double>>& robotPoses, const std::vector<int>& nodeIdxMin,
+                       const std::vector<int>& nodeIdxMax);
+    ~IcpReferenceSetHip();
+    IcpReferenceSetHip(const IcpReferenceSetHip&) = delete;
+    IcpReferenceSetHip& operator=(const IcpReferenceSetHip&) = delete;
+    int Size() const { return lgs_icp_ref_set_size(mSet); }
+    // borrowed: valid while this object lives
+    const lgs_icp_ref* Reference(int i) const { return lgs_icp_ref_set_ref(mSet, i); }
+    const lgs_icp_params& Params() const { return mParams; }
+    const DevicePtr& Dev() const { return mDev; }
+    lgs_icp_ref_set* Handle() const { return mSet; }
+
+private:
+    DevicePtr mDev;
+    lgs_icp_params mParams{};
+    lgs_icp_ref_set* mSet = nullptr;
+};
+
+// What an ICP refinement of a detected loop must meet to replace the
+// detector's estimate (lgs_loop_refine_gate); the defaults accept every refine
+// that found a pose
+struct LoopRefineGate {
+    int mMinPairs = 3;
+    double mMaxNormalizedCost = HUGE_VAL;
+    double mMaxTranslation = HUGE_VAL;
+    double mMaxRotation = HUGE_VAL;
+};
+
+// Detected loops refined by point-to-line ICP against their local maps'
+// references (lgs_loop_refine_icp).  `results` are those a
+// detector's Detect(queries, results) appended: the found nodes in query ->
+// node order, each recognised by (mStartNodeIdx, mEndNodeIdx).  A result's
+// estimate is Compound(query.mLocalMapNodePose, mRelativePose); query q is
+// refined against set.Reference(mapIndexOfQuery[q]).  An accepted result gets
+// the ICP's mRelativePose and mEstimatedCovMat, every other stays as it is.
+// Returns one flag per result: 1 refined, 0 kept.
+class LoopRefinerIcpHip {
+public:
+    explicit LoopRefinerIcpHip(const LoopRefineGate& gate = {});
+    std::vector<int> Refine(const IcpReferenceSetHip& set, const std::vector<int>& mapIndexOfQuery,
+                            const std::vector<LoopDetectionQuery>& queries,
+                            std::vector<LoopDetectionResult>& results);
+    // per result of the last Refine: the ICP's summary
+    const std::vector<lgs_icp_summary>& LastSummaries() const { return mLast; }
+    const lgs_loop_refine_gate& Gate() const { return mGate; }
+
+private:
+    lgs_loop_refine_gate mGate{};
+    std::vector<lgs_icp_summary> mLast;
 };
 
 // LoopDetectorBranchBound (C/mapping/loop_detector_branch_bound.cpp:10-117):

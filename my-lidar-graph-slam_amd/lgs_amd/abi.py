@@ -277,6 +277,12 @@ class LoopResult(C.Structure):
 LOOP_RESULT_DOUBLES = 22   # sizeof(lgs_loop_result) / 8
 
 
+class LoopRefineGate(C.Structure):
+    """lgs_loop_refine_gate: what an ICP refinement of a loop record must meet."""
+    _fields_ = [("min_pairs", C.c_int), ("max_normalized_cost", C.c_double), ("max_translation", C.c_double),
+                ("max_rotation", C.c_double)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("algo_bytes", C.c_double), ("dispatch_ms", C.c_double)]
@@ -494,6 +500,16 @@ _PROTOS = [
                                                   C.POINTER(IcpParams), C.POINTER(IcpSummary)]),
     ("lgs_icp_ref_pairs", C.c_int, [_P, _P, _P, Pose2D, C.POINTER(IcpParams), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_double)]),
+    ("lgs_icp_ref_set_create", C.c_int, [_P, C.POINTER(_P), C.POINTER(Pose2D), C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.c_int, C.POINTER(IcpParams), C.POINTER(_P)]),
+    ("lgs_icp_ref_set_destroy", None, [_P]),
+    ("lgs_icp_ref_set_size", C.c_int, [_P]),
+    ("lgs_icp_ref_set_ref", _P, [_P, C.c_int]),
+    ("lgs_icp_ref_set_stats", C.c_int, [_P] + [C.POINTER(C.c_longlong)] * 7),
+    ("lgs_icp_ref_set_last_build_ms", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("lgs_loop_refine_icp", C.c_int, [_P, C.POINTER(_P), C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
+                                      C.POINTER(IcpParams), C.POINTER(LoopRefineGate), C.POINTER(LoopResult),
+                                      C.POINTER(C.c_int), C.POINTER(IcpSummary)]),
     ("lgs_loop_graph_create", C.c_int, [_P, C.POINTER(Pose2D), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                         C.POINTER(_P)]),
     ("lgs_loop_graph_destroy", None, [_P]),
@@ -1050,6 +1066,53 @@ class Context:
         self.check(self.lib.lgs_icp_ref_create(self.h, arr, ps, n, C.byref(params), C.byref(h)), "icp_ref_create")
         return IcpRef(self, h)
 
+    def icp_ref_set(self, scans, poses, idx_min, idx_max, params: "IcpParams") -> "IcpRefSet":
+        """lgs_icp_ref_set_create: one reference per inclusive node range
+        idx_min[i] .. idx_max[i] of (scans, poses), all built in one pass
+        (DESIGN.md 4.5d); reference i equals icp_ref(scans[lo:hi + 1], poses[lo:hi + 1])."""
+        n, m = len(scans), len(idx_min)
+        arr = (_P * max(1, n))(*[s.h for s in scans])
+        ps = (Pose2D * max(1, n))(*[Pose2D(*p) for p in poses])
+        lo = (C.c_int * max(1, m))(*[int(v) for v in idx_min])
+        hi = (C.c_int * max(1, m))(*[int(v) for v in idx_max])
+        h = _P()
+        self.check(self.lib.lgs_icp_ref_set_create(self.h, arr, ps, n, lo, hi, m, C.byref(params), C.byref(h)),
+                   "icp_ref_set_create")
+        return IcpRefSet(self, h)
+
+    IcpRefSetStats = namedtuple("IcpRefSetStats", "builds table_launches count_launches scan_launches "
+                                                  "scatter_launches build_syncs refine_launches")
+
+    def icp_ref_set_stats(self):
+        """lgs_icp_ref_set_stats: this context's counters of set builds and refine launches"""
+        v = [C.c_longlong() for _ in range(7)]
+        self.check(self.lib.lgs_icp_ref_set_stats(self.h, *[C.byref(x) for x in v]), "icp_ref_set_stats")
+        return Context.IcpRefSetStats(*[x.value for x in v])
+
+    def icp_ref_set_last_build_ms(self):
+        """lgs_icp_ref_set_last_build_ms: (table pass, grids) of the last set build, host clock"""
+        a, b = C.c_double(), C.c_double()
+        self.check(self.lib.lgs_icp_ref_set_last_build_ms(self.h, C.byref(a), C.byref(b)), "icp_ref_set_last_build_ms")
+        return a.value, b.value
+
+    def loop_refine_icp(self, refs, queries, candidates, params: "IcpParams", gate: "LoopRefineGate", results):
+        """lgs_loop_refine_icp: refs[q] is query q's IcpRef; queries and candidates as loop_detect takes them
+        (a query's map and coarse grid may be None); results: a ctypes LoopResult array, refined in place.
+        Returns (refined flags, [IcpSummary] per candidate)."""
+        n = len(candidates)
+        qs = (LoopQuery * max(1, len(queries)))()
+        for i, (m, c, pose, idx, first, cnt) in enumerate(queries):
+            qs[i] = LoopQuery(m.h if m is not None else None, None, Pose2D(*pose), idx, first, cnt)
+        cs = (LoopCandidate * max(1, n))()
+        for i, (s, pose, idx) in enumerate(candidates):
+            cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
+        rarr = (_P * max(1, len(refs)))(*[r.h for r in refs])
+        refined = (C.c_int * max(1, n))()
+        sums = (IcpSummary * max(1, n))()
+        self.check(self.lib.lgs_loop_refine_icp(self.h, rarr, qs, len(queries), cs, n, C.byref(params), C.byref(gate),
+                                                results, refined, sums), "loop_refine_icp")
+        return list(refined)[:n], list(sums)[:n]
+
     def loop_graph(self, poses, idx_min, idx_max) -> "LoopGraph":
         """lgs_loop_graph_create: a graph snapshot (poses n x 2 or n x 3, the
         maps' inclusive node ranges) for the nearest-node loop searcher
@@ -1475,8 +1538,9 @@ class IcpRef:
     """lgs_icp_ref: the reference of the multi-scan point-to-line ICP."""
     RefInfo = namedtuple("RefInfo", "n_refs entries lines cells_x cells_y cell_size")
 
-    def __init__(self, ctx, h):
+    def __init__(self, ctx, h, borrowed: bool = False):
         self.ctx, self.h = ctx, h
+        self.borrowed = borrowed   # a member of an IcpRefSet: close() leaves it to the set
 
     def info(self):
         v = [C.c_int() for _ in range(5)]
@@ -1521,8 +1585,38 @@ class IcpRef:
         return k, j, residual
 
     def close(self):
-        if self.h:
+        if self.h and not self.borrowed:
             self.ctx.lib.lgs_icp_ref_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IcpRefSet:
+    """lgs_icp_ref_set: one IcpRef per local map, built in one pass; set[i] is a
+    view that lives as long as the set and whose close() does nothing."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+        self.n = ctx.lib.lgs_icp_ref_set_size(h)
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i) -> "IcpRef":
+        if not self.h:
+            raise ValueError("the reference set is closed")
+        if not -self.n <= i < self.n:
+            raise IndexError(i)
+        return IcpRef(self.ctx, _P(self.ctx.lib.lgs_icp_ref_set_ref(self.h, i % self.n)), borrowed=True)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lgs_icp_ref_set_destroy(self.h)
             self.h = None
 
     def __del__(self):

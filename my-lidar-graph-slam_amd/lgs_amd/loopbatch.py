@@ -253,6 +253,33 @@ def run_sharded_rccl(cands: Sequence[Candidate], detect_fn, gather: RcclGather) 
     return gather(n, lo, hi, local)
 
 
+def refine_icp(ctx: "abi.Context", ref_set, maps: Sequence[LocalMap], cands: Sequence[Candidate],
+               records: np.ndarray, prm: "abi.IcpParams", gate: "abi.LoopRefineGate",
+               ref_of_query: Optional[Sequence[int]] = None):
+    """lgs_loop_refine_icp over the record array run_sharded returns (uint8
+    [n, 176], candidate order): every found record is refined by ICP from its
+    estimate against its query's reference and, where the gate accepts it,
+    gets the ICP's estimate, loop edge, covariance and cost.
+    ref_set[i] is an abi.IcpRef (an abi.IcpRefSet, or a list); query q uses
+    ref_set[ref_of_query[q]], by default ref_set[q].  Of maps only node_pose
+    and node_index are read.  Returns (records, refined, summaries): a new
+    uint8 [n, 176] array, an int array [n] and the candidates' IcpSummary list."""
+    n = len(cands)
+    assert records.shape == (n, RECORD_BYTES)
+    ref_of_query = list(range(len(maps))) if ref_of_query is None else list(ref_of_query)
+    scans = [ctx.scan(c.ranges, c.angles) for c in cands]
+    queries = [(None, None, maps[q].node_pose, maps[q].node_index, first, count)
+               for q, first, count in sub_queries(cands, 0, n)]
+    refs = [ref_set[ref_of_query[q]] for q, _, _ in sub_queries(cands, 0, n)]
+    cl = [(scans[i], c.pose, c.node_index) for i, c in enumerate(cands)]
+    out = (abi.LoopResult * max(1, n)).from_buffer_copy(records.tobytes() if n else bytes(RECORD_BYTES))
+    refined, sums = ctx.loop_refine_icp(refs, queries, cl, prm, gate, out)
+    for s in scans:
+        s.close()
+    new = np.frombuffer(bytes(out), dtype=np.uint8)[: n * RECORD_BYTES].reshape(n, RECORD_BYTES).copy()
+    return new, np.array(refined, dtype=np.int32), sums
+
+
 def decode(records: np.ndarray) -> List[abi.LoopResult]:
     raw = records.tobytes()
     return [abi.LoopResult.from_buffer_copy(raw[i * RECORD_BYTES:(i + 1) * RECORD_BYTES])

@@ -12,6 +12,10 @@ Prints one JSON line per measurement:
           reference of --ref-scans K scans: lgs_icp_ref_create's
           time, the lone refine, the batch of 256 (K = 1: the bytes of `lone`)
   k4      lgs_linsolve_optimize_pose (lone p50 / p90) and _batch of 256
+With --ref-set M [M ...] instead, one line per M:
+  ref_set lgs_icp_ref_set_create of M references x 10 scans and
+          its two halves (table pass, grids), M lgs_icp_ref_create calls over
+          the same ranges in the same run, lgs_loop_refine_icp per candidate
 
 The GPU measurements run in one child process under a time limit; a child that
 fails or times out ends the run.
@@ -180,6 +184,93 @@ def gpu_step(args):
     ctx.close()
 
 
+REF_SET_SCANS = 10   # scans per local map of --ref-set
+
+
+def ref_set_step(args):
+    """--ref-set: per M, lgs_icp_ref_set_create of M references x 10 scans against M lgs_icp_ref_create calls
+    over the same ranges, alternating in one process, and lgs_loop_refine_icp with one candidate per map.
+    Every timed call ends in a host wait on the stream; the host clock is around the whole call."""
+    from lgs_amd import abi, scene
+    world = scene.make_world()
+    ang = scene.beam_angles(args.beams)
+    rng = np.random.default_rng(17)
+    ctx = abi.Context(0)
+    P = abi.IcpParams(*ICP)
+    m_max = max(args.ref_set)
+    poses, scans, truths, cands = [], [], [], []
+    for i in range(m_max):
+        c = (rng.uniform(-1.5, 1.5), rng.uniform(-1.5, 1.5))
+        for p in scene.arc_poses(REF_SET_SCANS, center=c):
+            poses.append(tuple(p))
+            scans.append(ctx.scan(scene.ray_cast(world, p, ang), ang))
+        true = (c[0] + rng.uniform(-0.5, 0.5), c[1] + rng.uniform(-0.5, 0.5), rng.uniform(-np.pi, np.pi))
+        truths.append(true)
+        cands.append(ctx.scan(scene.ray_cast(world, true, ang), ang))
+    for M in args.ref_set:
+        lo = [REF_SET_SCANS * i for i in range(M)]
+        hi = [a + REF_SET_SCANS - 1 for a in lo]
+        n = REF_SET_SCANS * M
+
+        def lone_creates():
+            return [ctx.icp_ref(scans[a:b + 1], poses[a:b + 1], P) for a, b in zip(lo, hi)]
+
+        t_set, t_lone, split = [], [], []
+        for k in range(-args.warmup, args.steps):   # the two paths alternate
+            t0 = time.perf_counter()
+            rset = ctx.icp_ref_set(scans[:n], poses[:n], lo, hi, P)
+            t1 = time.perf_counter()
+            handles = lone_creates()
+            t2 = time.perf_counter()
+            if k >= 0:
+                t_set.append(t1 - t0)
+                t_lone.append(t2 - t1)
+                split.append(ctx.icp_ref_set_last_build_ms())
+            same = all(rset[i].info() == handles[i].info() for i in range(M))
+            for h in handles:
+                h.close()
+            if k < args.steps - 1:
+                rset.close()
+        entries = sum(rset[i].info().entries for i in range(M))
+        cells = sum(rset[i].info().cells_x * rset[i].info().cells_y for i in range(M))
+        # one candidate per map, its record 5 cm and 0.02 rad off the truth
+        queries = [(None, None, poses[lo[i]], lo[i], i, 1) for i in range(M)]
+        cl = [(cands[i], truths[i], n + i) for i in range(M)]
+        gate = abi.LoopRefineGate(3, float("inf"), float("inf"), float("inf"))
+
+        def records():
+            recs = (abi.LoopResult * M)()
+            for i, t in enumerate(truths[:M]):
+                recs[i].found = 1
+                recs[i].estimated_pose = abi.Pose2D(t[0] + 0.05, t[1] - 0.03, t[2] + 0.02)
+            return recs
+
+        refs = [rset[i] for i in range(M)]
+        t_ref = []
+        for k in range(-args.warmup, args.steps):
+            recs = records()
+            t0 = time.perf_counter()
+            refined, sums = ctx.loop_refine_icp(refs, queries, cl, P, gate, recs)
+            if k >= 0:
+                t_ref.append(time.perf_counter() - t0)
+        err = [float(np.hypot(recs[i].estimated_pose.x - truths[i][0], recs[i].estimated_pose.y - truths[i][1]))
+               for i in range(M) if refined[i]]
+        rset.close()
+        med = lambda t: float(np.median(t))
+        print(json.dumps(dict(line="ref_set", refs=M, scans_per_ref=REF_SET_SCANS, beams=len(ang), entries=entries,
+                              cells=cells, timed_calls=args.steps,
+                              set_create_ms=round(1e3 * med(t_set), 3), set_create_ms_min_max=[round(1e3 * min(t_set), 3), round(1e3 * max(t_set), 3)],
+                              set_table_pass_ms=round(float(np.median([s[0] for s in split])), 3),
+                              set_grids_ms=round(float(np.median([s[1] for s in split])), 3),
+                              lone_creates_ms=round(1e3 * med(t_lone), 3), lone_creates_ms_min_max=[round(1e3 * min(t_lone), 3), round(1e3 * max(t_lone), 3)],
+                              lone_create_us_each=round(1e6 * med(t_lone) / M, 1),
+                              set_over_lone=round(med(t_set) / med(t_lone), 4), same_info=bool(same),
+                              refine_call_ms=round(1e3 * med(t_ref), 3), refine_us_per_candidate=round(1e6 * med(t_ref) / M, 2),
+                              refined=int(sum(refined)), steps=ICP[0], median_error_m=float(np.median(err)) if err else None)),
+              flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--beams", type=int, default=1081)
@@ -188,13 +279,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--ref-scans", type=int, default=1, help="reference scans per lgs_icp_ref (the ref path)")
     ap.add_argument("--timeout", type=float, default=240.0, help="time limit of the GPU step (s)")
+    ap.add_argument("--ref-set", type=int, nargs="+", metavar="M",
+                    help="instead of the lines above: per M, one lgs_icp_ref_set_create of M references x 10 scans "
+                         "against M lgs_icp_ref_create calls, and lgs_loop_refine_icp per candidate (DESIGN.md 4.5d)")
     ap.add_argument("--step", choices=["gpu"], help=argparse.SUPPRESS)   # child mode
     args = ap.parse_args()
+    if args.ref_set and min(args.ref_set) < 1:
+        ap.error("--ref-set: at least one reference")
     if args.step:
-        gpu_step(args)
+        if args.ref_set:
+            ref_set_step(args)
+        else:
+            gpu_step(args)
         return 0
     cmd = [sys.executable, os.path.abspath(__file__), "--step", "gpu", "--beams", str(args.beams), "--lone",
            str(args.lone), "--steps", str(args.steps), "--warmup", str(args.warmup), "--ref-scans", str(args.ref_scans)]
+    if args.ref_set:
+        cmd += ["--ref-set"] + [str(m) for m in args.ref_set]
     try:
         rc = subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
