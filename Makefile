@@ -27,6 +27,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_icp
 	$(MAKE) -C tests/cpp_icp_ref
 	$(MAKE) -C tests/cpp_icp_ref_set
+	$(MAKE) -C tests/cpp_icp_window
 	$(MAKE) -C tests/cpp_loop_search
 	$(MAKE) -C tests/cpp_hv
 	$(MAKE) -C tests/cpp_loop
@@ -48,6 +49,7 @@ clean:
 	$(MAKE) -C tests/cpp_icp clean
 	$(MAKE) -C tests/cpp_icp_ref clean
 	$(MAKE) -C tests/cpp_icp_ref_set clean
+	$(MAKE) -C tests/cpp_icp_window clean
 	$(MAKE) -C tests/cpp_loop_search clean
 	$(MAKE) -C tests/cpp_hv clean
 	$(MAKE) -C tests/cpp_loop clean

@@ -1255,6 +1255,76 @@ int  lgs_loop_refine_icp(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs
                          const lgs_loop_refine_gate* gate, lgs_loop_result* results, int* refined,
                          lgs_icp_summary* summaries);
 
+/* ---- ICP loop detector: a window search of start poses (k_icp_window.hip) ----
+ * The lattice.  nx = 2 * half_x + 1 poses along x, ny and nt likewise,
+ * P = nx * ny * nt per candidate.  Lattice index p = (it * ny + iy) * nx + ix
+ * (theta outermost, x innermost).  The robot pose of p around a centre c is
+ *   ( c.x     + (double)(ix - half_x)     * step_xy,
+ *     c.y     + (double)(iy - half_y)     * step_xy,
+ *     c.theta + (double)(it - half_theta) * step_theta ),
+ * each product and each sum rounded once, nothing contracted; the coordinate
+ * of the centre index (ix == half_x, ...) is c's own, bit for bit.  The sensor
+ * pose is Compound(lattice pose, the scan's relative sensor pose) with glibc's
+ * sincos.
+ * The score.  cost[p] and pairs[p] are byte for byte the initial_cost and
+ * initial_pairs that lgs_icp_ref_optimize_pose(ctx, ref, scan, lattice pose p,
+ * params, ...) returns: the first pass of 4.5b at that sensor pose over the
+ * table of 4.5c, summed in 4.5b's tree.
+ * The selection.  The best pose p* is the lexicographic minimum of (cost, p):
+ * p wins iff cost < best || (cost == best && p < p*), from (+inf, -1).  Ties go
+ * to the lowest index, neither NaN nor +inf wins, and p* = -1 if nothing wins.
+ * LGS_ERR_INVALID_ARG, before any device work: a NULL argument (the optional
+ * outputs apart), a half outside 0 .. 512, a step that is not finite or <= 0,
+ * P > LGS_ICP_WINDOW_MAX_POSES, a scan of more than LGS_ICP_WINDOW_MAX_BEAMS
+ * beams, a centre or an outermost lattice coordinate that is not finite, the
+ * refine-time rules of lgs_icp_ref_* (context, bitwise-equal table parameters,
+ * an empty scan), and for the detector the query-cover rule and the gate rules
+ * of lgs_loop_refine_icp.  An angle outside the restated sincos domain (a
+ * lattice theta included) fails with LGS_ERR_INTERNAL.  A failing call writes
+ * nothing to its outputs. */
+typedef struct {
+    int    half_x, half_y, half_theta;   /* 2h + 1 poses per axis, each h in 0 .. 512 */
+    double step_xy, step_theta;          /* finite, > 0 */
+} lgs_icp_window;
+#define LGS_ICP_WINDOW_MAX_POSES 1048576  /* per candidate */
+#define LGS_ICP_WINDOW_MAX_BEAMS 4096     /* beams of the scanned scan */
+size_t lgs_icp_window_size(void);    /* sizeof, for bindings */
+/* The dense scores of one window: cost[P] and pairs[P] in lattice order.  One
+ * launch and one wait on the stream. */
+int  lgs_icp_ref_window_scores(lgs_ctx* ctx, const lgs_icp_ref* ref, const lgs_scan* scan, lgs_pose2d centre,
+                               const lgs_icp_window* window, const lgs_icp_params* params, double* cost, int* pairs);
+/* The detector.  Queries and candidates follow the rules of
+ * lgs_loop_refine_icp; of a query only local_map_node_pose,
+ * local_map_node_index, first_candidate and num_candidates are read (map and
+ * coarse may be NULL).  For candidate c of query q the window is centred on
+ * candidates[c].node_pose against refs[q]; that gives p*.  If p* >= 0 one
+ * refine starts from lattice pose p*, and all candidates' refines run as one
+ * lgs_icp_ref_optimize_pose_batch.  The gate is lgs_loop_refine_icp's, with the
+ * start lattice pose in the place of the record's estimate, so max_translation
+ * and max_rotation bound how far the refine may wander from where the window
+ * put it.  results[c], as the other detectors write one: all 176 bytes zero,
+ * then start_node_index, end_node_index and start_node_pose; if a refine ran,
+ * estimated_pose, normalized_cost and covariance of its summary and score =
+ * (double)num_pairs / (double)NumOfScans(); found = 1 iff the gate accepts, and
+ * only then relative_pose = InverseCompound(local_map_node_pose,
+ * estimated_pose).  best_index (may be NULL) receives p* per candidate,
+ * summaries (may be NULL) the refines' summaries, zero bytes where none ran.
+ * With all three halves 0 the detector is "refine from the node pose".
+ * One score launch and one wait per chunk of candidates (a chunk holds
+ * max(1, 67108864 / P) candidates: 64 or more), then one wait for the refines:
+ * two waits per call below that cap, whatever the number of candidates.
+ * num_candidates = 0 is legal and does no device work. */
+int  lgs_loop_detect_icp(lgs_ctx* ctx, const lgs_icp_ref* const* refs, const lgs_loop_query* queries, int num_queries,
+                         const lgs_loop_candidate* candidates, int num_candidates, const lgs_icp_params* params,
+                         const lgs_icp_window* window, const lgs_loop_refine_gate* gate, lgs_loop_result* results,
+                         int* best_index, lgs_icp_summary* summaries);
+/* Counters of this context since its creation (each may be NULL): calls of the
+ * two entry points above that reached the device, launches of the score
+ * kernel, host waits on the stream made by those calls (refines included), and
+ * launches of the refine kernel made by lgs_loop_detect_icp. */
+int  lgs_icp_window_stats(const lgs_ctx* ctx, long long* calls, long long* score_launches, long long* syncs,
+                          long long* refine_launches);
+
 /* ---- nearest-node loop searcher (k_loop_search.hip) ----
  * LoopSearcherNearest::Search (C/mapping/loop_searcher_nearest.cpp:13-108) over
  * flat arrays, batched over hints.  A graph snapshot is poses[n] (node k has

@@ -92,6 +92,7 @@ enum Slot {
     S_PG2, S_PG3,   // resident pose-graph LM (k_pglm.hip): incidence lists and edges; poses, loss terms, step record
     S_ICP0, S_ICP1, // point-to-line ICP (k_icp.hip): records, trajectory, error word; lgs_icp_pairs' outputs
     S_ICPR0,        // lgs_icp_ref_create (k_icp_ref.hip): per-scan boxes and the cell counts of a build
+    S_ICPW0, S_ICPW1,   // ICP window search (k_icp_window.hip): partials and error word; dense cost and pairs
     S_LOOPS0, S_LOOPS1,   // loop search (k_loop_search.hip): cuts and group partials; records and the per-map table
     // bank 1 of the per-batch buffers: a batched call keeps two 64-query
     // chunks in flight (the next chunk's launches go out before the host
@@ -473,6 +474,8 @@ struct lgs_ctx {
     // (set builds that reached the device, launches of the four build kernels, host waits of the builds,
     // launches of k_icp_ref by any lgs_icp_ref_* refine)
     long long icpset_builds = 0, icpset_launches[4] = {}, icpset_syncs = 0, icpref_refine_launches = 0;
+    // lgs_icp_ref_window_scores / lgs_loop_detect_icp (k_icp_window.hip): the counters of lgs_icp_window_stats
+    long long icpwin_calls = 0, icpwin_score_launches = 0, icpwin_syncs = 0, icpwin_refine_launches = 0;
     double icpset_last_ms[2] = {};   // the last build's host clock: up to the first wait (table), from there on (grids)
     // padded phase-plane buffer (per bank): margins zeroed once per (buffer, layout, set count)
     void* planes_ptr[2] = {};

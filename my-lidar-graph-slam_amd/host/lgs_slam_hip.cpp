@@ -893,6 +893,65 @@ std::vector<int> LoopRefinerIcpHip::Refine(const IcpReferenceSetHip& set, const 
     return flags;
 }
 
+// -------------------------------------------------------- LoopDetectorIcpHip
+LoopDetectorIcpHip::LoopDetectorIcpHip(const IcpPointToLineParams& p, const IcpWindow& w, const LoopRefineGate& g)
+{
+    mParams = { p.mNumOfIterationsMax, p.mConvergenceThreshold, p.mUsableRangeMin, p.mUsableRangeMax,
+                p.mTranslationRegularizer, p.mRotationRegularizer, p.mMaxCorrespondenceDist, p.mMaxSegmentLength };
+    mWindow = { w.mHalfX, w.mHalfY, w.mHalfTheta, w.mStepXY, w.mStepTheta };
+    mGate = { g.mMinPairs, g.mMaxNormalizedCost, g.mMaxTranslation, g.mMaxRotation };
+}
+
+void LoopDetectorIcpHip::Detect(const IcpReferenceSetHip& set, const std::vector<int>& mapIndexOfQuery,
+                                const std::vector<LoopDetectionQuery>& queries,
+                                std::vector<LoopDetectionResult>& results)
+{
+    if (mapIndexOfQuery.size() != queries.size())
+        throw Error(LGS_ERR_INVALID_ARG, "LoopDetectorIcpHip: need one map index per query");
+    results.clear();
+    mLastBest.clear();
+    mLast.clear();
+    std::vector<const lgs_icp_ref*> refs;
+    std::vector<lgs_loop_query> qs;
+    std::vector<lgs_loop_candidate> cs;
+    for (std::size_t q = 0; q < queries.size(); ++q) {
+        const LoopDetectionQuery& Q = queries[q];
+        const lgs_icp_ref* ref = set.Reference(mapIndexOfQuery[q]);
+        if (!ref) throw Error(LGS_ERR_INVALID_ARG, "LoopDetectorIcpHip: map index outside the reference set");
+        refs.push_back(ref);
+        lgs_loop_query c{};
+        c.local_map_node_pose = to_c(Q.mLocalMapNodePose);
+        c.local_map_node_index = Q.mLocalMapNodeIndex;
+        c.first_candidate = (int)cs.size();
+        c.num_candidates = (int)Q.mPoseGraphNodes.size();
+        qs.push_back(c);
+        for (const auto& n : Q.mPoseGraphNodes) {
+            if (!n.mScanData) throw Error(LGS_ERR_INVALID_ARG, "LoopDetectorIcpHip: null scan");
+            cs.push_back(lgs_loop_candidate{ n.mScanData->Handle(), to_c(n.mPose), n.mIndex, 0 });
+        }
+    }
+    if (cs.empty()) return;
+    std::vector<lgs_loop_result> out(cs.size());
+    std::vector<int> best(cs.size(), -1);
+    std::vector<lgs_icp_summary> sums(cs.size());
+    set.Dev()->Check(lgs_loop_detect_icp(set.Dev()->Handle(), refs.data(), qs.data(), (int)qs.size(), cs.data(),
+                                         (int)cs.size(), &mParams, &mWindow, &mGate, out.data(), best.data(),
+                                         sums.data()),
+                     "lgs_loop_detect_icp");
+    mLastBest = std::move(best);
+    mLast = std::move(sums);
+    for (const auto& r : out) {
+        if (!r.found) continue;
+        LoopDetectionResult o;
+        o.mRelativePose = from_c(r.relative_pose);
+        o.mStartNodePose = from_c(r.start_node_pose);
+        o.mStartNodeIdx = r.start_node_index;
+        o.mEndNodeIdx = r.end_node_index;
+        o.mEstimatedCovMat = cov_of(r.covariance);
+        results.push_back(o);
+    }
+}
+
 // ---------------------------------------------------- LoopSearcherNearestHip
 namespace {
 

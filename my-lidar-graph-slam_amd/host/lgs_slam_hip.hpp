@@ -576,6 +576,40 @@ private:
     std::vector<lgs_icp_summary> mLast;
 };
 
+// The lattice of start poses of the ICP loop detector (lgs_icp_window):
+// 2 * half + 1 poses per axis around a candidate's node pose
+struct IcpWindow {
+    int mHalfX = 0, mHalfY = 0, mHalfTheta = 0;
+    double mStepXY = 0.05, mStepTheta = 0.005;
+};
+
+// A loop detector that needs no grid (lgs_loop_detect_icp):
+// every node's scan is scored by one ICP pass at each pose of the window around
+// its pose against set.Reference(mapIndexOfQuery[q]), refined from the best of
+// them and accepted by the gate; the found ones are appended in query -> node
+// order, like the other detectors'.  Of a query mLocalMap and mPrecomputedMap
+// are not read.
+class LoopDetectorIcpHip {
+public:
+    LoopDetectorIcpHip(const IcpPointToLineParams& params, const IcpWindow& window, const LoopRefineGate& gate = {});
+    void Detect(const IcpReferenceSetHip& set, const std::vector<int>& mapIndexOfQuery,
+                const std::vector<LoopDetectionQuery>& queries, std::vector<LoopDetectionResult>& results);
+    // per candidate node of the last Detect, in query -> node order: the best
+    // lattice index (-1: none) and the refine's summary (zero: none ran)
+    const std::vector<int>& LastBestIndices() const { return mLastBest; }
+    const std::vector<lgs_icp_summary>& LastSummaries() const { return mLast; }
+    const lgs_icp_params& Params() const { return mParams; }
+    const lgs_icp_window& Window() const { return mWindow; }
+    const lgs_loop_refine_gate& Gate() const { return mGate; }
+
+private:
+    lgs_icp_params mParams{};
+    lgs_icp_window mWindow{};
+    lgs_loop_refine_gate mGate{};
+    std::vector<int> mLastBest;
+    std::vector<lgs_icp_summary> mLast;
+};
+
 // LoopDetectorBranchBound (C/mapping/loop_detector_branch_bound.cpp:10-117):
 // pyramids computed per query (LocalMapInfo caches them, :45-55), every node
 // matched, found ones appended in query -> node order.

@@ -283,6 +283,26 @@ class LoopRefineGate(C.Structure):
                 ("max_rotation", C.c_double)]
 
 
+class IcpWindow(C.Structure):
+    """lgs_icp_window: the lattice of start poses of the ICP loop detector:
+    2 * half + 1 poses per axis around a centre, theta outermost and x innermost."""
+    _fields_ = [("half_x", C.c_int), ("half_y", C.c_int), ("half_theta", C.c_int), ("step_xy", C.c_double),
+                ("step_theta", C.c_double)]
+
+    @property
+    def shape(self):
+        """(nt, ny, nx)"""
+        return 2 * self.half_theta + 1, 2 * self.half_y + 1, 2 * self.half_x + 1
+
+    def pose(self, centre, p: int):
+        """the robot pose of lattice index p around `centre` (the centre index gives the centre itself)"""
+        nt, ny, nx = self.shape
+        ix, iy, it = p % nx, (p // nx) % ny, p // (nx * ny)
+        f = lambda c, i, h, step: float(c) if i == h else float(c) + float(i - h) * step
+        return (f(centre[0], ix, self.half_x, self.step_xy), f(centre[1], iy, self.half_y, self.step_xy),
+                f(centre[2], it, self.half_theta, self.step_theta))
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("algo_bytes", C.c_double), ("dispatch_ms", C.c_double)]
@@ -510,6 +530,13 @@ _PROTOS = [
     ("lgs_loop_refine_icp", C.c_int, [_P, C.POINTER(_P), C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
                                       C.POINTER(IcpParams), C.POINTER(LoopRefineGate), C.POINTER(LoopResult),
                                       C.POINTER(C.c_int), C.POINTER(IcpSummary)]),
+    ("lgs_icp_window_size", C.c_size_t, []),
+    ("lgs_icp_ref_window_scores", C.c_int, [_P, _P, _P, Pose2D, C.POINTER(IcpWindow), C.POINTER(IcpParams),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("lgs_loop_detect_icp", C.c_int, [_P, C.POINTER(_P), C.POINTER(LoopQuery), C.c_int, C.POINTER(LoopCandidate), C.c_int,
+                                      C.POINTER(IcpParams), C.POINTER(IcpWindow), C.POINTER(LoopRefineGate),
+                                      C.POINTER(LoopResult), C.POINTER(C.c_int), C.POINTER(IcpSummary)]),
+    ("lgs_icp_window_stats", C.c_int, [_P] + [C.POINTER(C.c_longlong)] * 4),
     ("lgs_loop_graph_create", C.c_int, [_P, C.POINTER(Pose2D), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                         C.POINTER(_P)]),
     ("lgs_loop_graph_destroy", None, [_P]),
@@ -1112,6 +1139,43 @@ class Context:
         self.check(self.lib.lgs_loop_refine_icp(self.h, rarr, qs, len(queries), cs, n, C.byref(params), C.byref(gate),
                                                 results, refined, sums), "loop_refine_icp")
         return list(refined)[:n], list(sums)[:n]
+
+    def icp_window_scores(self, ref: "IcpRef", scan, centre, window: "IcpWindow", params: "IcpParams"):
+        """lgs_icp_ref_window_scores: (cost float64, pairs int32), each shaped [nt, ny, nx]: what
+        ref.refine(scan, window.pose(centre, p), params) reports as initial_cost / initial_pairs"""
+        shape = window.shape
+        cost, pairs = np.zeros(shape), np.zeros(shape, dtype=np.int32)
+        self.check(self.lib.lgs_icp_ref_window_scores(self.h, ref.h, scan.h, Pose2D(*centre), C.byref(window),
+                                                      C.byref(params), dptr(cost),
+                                                      pairs.ctypes.data_as(C.POINTER(C.c_int))), "icp_ref_window_scores")
+        return cost, pairs
+
+    def loop_detect_icp(self, refs, queries, candidates, params: "IcpParams", window: "IcpWindow",
+                        gate: "LoopRefineGate"):
+        """lgs_loop_detect_icp: refs[q] is query q's IcpRef; queries and candidates as loop_refine_icp takes them.
+        Returns (ctypes LoopResult array, [best lattice index] and [IcpSummary] per candidate)."""
+        n = len(candidates)
+        qs = (LoopQuery * max(1, len(queries)))()
+        for i, (m, c, pose, idx, first, cnt) in enumerate(queries):
+            qs[i] = LoopQuery(m.h if m is not None else None, None, Pose2D(*pose), idx, first, cnt)
+        cs = (LoopCandidate * max(1, n))()
+        for i, (s, pose, idx) in enumerate(candidates):
+            cs[i] = LoopCandidate(s.h, Pose2D(*pose), idx, 0)
+        rarr = (_P * max(1, len(refs)))(*[r.h for r in refs])
+        out = (LoopResult * max(1, n))()
+        best = (C.c_int * max(1, n))()
+        sums = (IcpSummary * max(1, n))()
+        self.check(self.lib.lgs_loop_detect_icp(self.h, rarr, qs, len(queries), cs, n, C.byref(params), C.byref(window),
+                                                C.byref(gate), out, best, sums), "loop_detect_icp")
+        return out, list(best)[:n], list(sums)[:n]
+
+    IcpWindowStats = namedtuple("IcpWindowStats", "calls score_launches syncs refine_launches")
+
+    def icp_window_stats(self):
+        """lgs_icp_window_stats: this context's counters of window searches"""
+        v = [C.c_longlong() for _ in range(4)]
+        self.check(self.lib.lgs_icp_window_stats(self.h, *[C.byref(x) for x in v]), "icp_window_stats")
+        return Context.IcpWindowStats(*[x.value for x in v])
 
     def loop_graph(self, poses, idx_min, idx_max) -> "LoopGraph":
         """lgs_loop_graph_create: a graph snapshot (poses n x 2 or n x 3, the

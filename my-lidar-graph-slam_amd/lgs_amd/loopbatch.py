@@ -180,6 +180,34 @@ def hip_detect_fn_gs(ctx: "abi.Context", maps: Sequence[LocalMap], cands: Sequen
     return fn
 
 
+def hip_detect_fn_icp(ctx: "abi.Context", ref_set, maps: Sequence[LocalMap], cands: Sequence[Candidate],
+                      prm: "abi.IcpParams", window: "abi.IcpWindow", gate: "abi.LoopRefineGate",
+                      ref_of_query: Optional[Sequence[int]] = None
+                      ) -> Callable[[List[Tuple[int, int, int]], int, int], np.ndarray]:
+    """As hip_detect_fn with the ICP loop detector (lgs_loop_detect_icp, DESIGN.md
+    4.5e): no grid at all.  ref_set[i] is an abi.IcpRef (an abi.IcpRefSet, or a
+    list); query q uses ref_set[ref_of_query[q]], by default ref_set[q].  Of maps
+    only node_pose and node_index are read.  fn.best and fn.summaries keep the
+    last call's best lattice indices and IcpSummary list."""
+    ref_of_query = list(range(len(maps))) if ref_of_query is None else list(ref_of_query)
+    scans = {}
+
+    def fn(subq, lo, hi):
+        queries = [(None, None, maps[q].node_pose, maps[q].node_index, first, count) for q, first, count in subq]
+        refs = [ref_set[ref_of_query[q]] for q, _, _ in subq]
+        cl = []
+        for i in range(lo, hi):
+            c = cands[i]
+            if i not in scans:
+                scans[i] = ctx.scan(c.ranges, c.angles)
+            cl.append((scans[i], c.pose, c.node_index))
+        out, fn.best, fn.summaries = ctx.loop_detect_icp(refs, queries, cl, prm, window, gate)
+        return np.frombuffer(bytes(out), dtype=np.uint8)[: (hi - lo) * RECORD_BYTES].reshape(hi - lo, RECORD_BYTES)
+
+    fn.best, fn.summaries = [], []
+    return fn
+
+
 def run_sharded(cands: Sequence[Candidate], detect_fn, rank: int = 0, world: int = 1, dist=None,
                 device=None) -> np.ndarray:
     """All candidates' records (uint8 [n, 176]) in candidate order, on every rank."""

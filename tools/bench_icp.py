@@ -16,6 +16,15 @@ With --ref-set M [M ...] instead, one line per M:
   ref_set lgs_icp_ref_set_create of M references x 10 scans and
           its two halves (table pass, grids), M lgs_icp_ref_create calls over
           the same ranges in the same run, lgs_loop_refine_icp per candidate
+With --window HX HY HT instead, one line:
+  window  the window search of start poses over (2 HX + 1) x
+          (2 HY + 1) x (2 HT + 1) lattice poses, three ways in alternating
+          rounds: (A) lgs_icp_ref_optimize_pose_batch over all lattice poses
+          with num_iterations_max = 1, reading initial_cost -- the only way to
+          score a window without the window kernel; (B)
+          lgs_icp_ref_window_scores over the same lattice (compared with A byte
+          for byte before anything is timed); (C) lgs_loop_detect_icp for 64
+          candidates against 10-scan references
 
 The GPU measurements run in one child process under a time limit; a child that
 fails or times out ends the run.
@@ -271,6 +280,115 @@ def ref_set_step(args):
     ctx.close()
 
 
+WINDOW_STEPS = (0.05, 0.01)   # m, rad
+WINDOW_MAPS, WINDOW_CANDS = 8, 64
+
+
+def window_step(args):
+    """--window: A, B and C of the module's comment.  Every timed call ends in a host wait on the stream; the
+    host clock is around the C call alone (its arrays are made before)."""
+    import ctypes as C
+    from lgs_amd import abi, scene
+    world = scene.make_world()
+    ang = scene.beam_angles(args.beams)
+    rng = np.random.default_rng(23)
+    ctx = abi.Context(0)
+    P = abi.IcpParams(*ICP)
+    P1 = abi.IcpParams(1, *ICP[1:])
+    hx, hy, ht = args.window
+    win = abi.IcpWindow(hx, hy, ht, *WINDOW_STEPS)
+    nt, ny, nx = win.shape
+    n_poses = nt * ny * nx
+    poses, scans, lo = [], [], []
+    for i in range(WINDOW_MAPS):
+        c = (rng.uniform(-1.5, 1.5), rng.uniform(-1.5, 1.5))
+        lo.append(len(scans))
+        for p in scene.arc_poses(REF_SET_SCANS, center=c):
+            poses.append(tuple(p))
+            scans.append(ctx.scan(scene.ray_cast(world, p, ang), ang))
+    hi = [a + REF_SET_SCANS - 1 for a in lo]
+    rset = ctx.icp_ref_set(scans, poses, lo, hi, P)
+    truths, nodes, cands, query_of = [], [], [], []
+    for k in range(WINDOW_CANDS):
+        q = k * WINDOW_MAPS // WINDOW_CANDS
+        c = poses[lo[q]]
+        true = (c[0] + rng.uniform(-0.5, 0.5), c[1] + rng.uniform(-0.5, 0.5), rng.uniform(-np.pi, np.pi))
+        # the drift stays inside the window
+        node = tuple(t + rng.uniform(-0.8, 0.8) * h * st for t, h, st in
+                     zip(true, (hx, hy, ht), (WINDOW_STEPS[0], WINDOW_STEPS[0], WINDOW_STEPS[1])))
+        truths.append(true)
+        nodes.append(node)
+        cands.append(ctx.scan(scene.ray_cast(world, true, ang), ang))
+        query_of.append(q)
+    # A and B score candidate 0's window
+    ref0 = rset[query_of[0]]
+    a_refs = (C.c_void_p * n_poses)(*[ref0.h] * n_poses)
+    a_scans = (C.c_void_p * n_poses)(*[cands[0].h] * n_poses)
+    a_init = (abi.Pose2D * n_poses)(*[abi.Pose2D(*win.pose(nodes[0], p)) for p in range(n_poses)])
+    a_out = (abi.IcpSummary * n_poses)()
+    b_cost, b_pairs = np.zeros(n_poses), np.zeros(n_poses, dtype=np.int32)
+
+    def run_a():
+        ctx.check(ctx.lib.lgs_icp_ref_optimize_pose_batch(ctx.h, a_refs, a_scans, a_init, n_poses, C.byref(P1), a_out),
+                  "icp_ref_optimize_pose_batch")
+
+    def run_b():
+        ctx.check(ctx.lib.lgs_icp_ref_window_scores(ctx.h, ref0.h, cands[0].h, abi.Pose2D(*nodes[0]), C.byref(win),
+                                                    C.byref(P), abi.dptr(b_cost),
+                                                    b_pairs.ctypes.data_as(C.POINTER(C.c_int))), "icp_ref_window_scores")
+
+    # C: all candidates, queries in map order
+    qs = (abi.LoopQuery * WINDOW_MAPS)()
+    per = WINDOW_CANDS // WINDOW_MAPS
+    for q in range(WINDOW_MAPS):
+        qs[q] = abi.LoopQuery(None, None, abi.Pose2D(*poses[lo[q]]), lo[q], q * per, per)
+    cs = (abi.LoopCandidate * WINDOW_CANDS)(*[abi.LoopCandidate(cands[k].h, abi.Pose2D(*nodes[k]), 1000 + k, 0)
+                                              for k in range(WINDOW_CANDS)])
+    c_refs = (C.c_void_p * WINDOW_MAPS)(*[rset[q].h for q in range(WINDOW_MAPS)])
+    gate = abi.LoopRefineGate(args.beams // 4, float("inf"), 0.5, 0.2)
+    c_out = (abi.LoopResult * WINDOW_CANDS)()
+    c_best = (C.c_int * WINDOW_CANDS)()
+
+    def run_c():
+        ctx.check(ctx.lib.lgs_loop_detect_icp(ctx.h, c_refs, qs, WINDOW_MAPS, cs, WINDOW_CANDS, C.byref(P), C.byref(win),
+                                              C.byref(gate), c_out, c_best, None), "loop_detect_icp")
+
+    run_a()
+    run_b()
+    same = bool(np.array_equal(np.array([o.initial_cost for o in a_out]).view(np.uint64), b_cost.view(np.uint64)) and
+                [o.initial_pairs for o in a_out] == b_pairs.tolist())
+    if not same:
+        print(json.dumps(dict(line="window", error="A and B differ")), flush=True)
+        sys.exit(1)
+    t = {"a": [], "b": [], "c": []}
+    for k in range(-args.warmup, args.steps):   # the three alternate
+        for name, fn in (("a", run_a), ("b", run_b), ("c", run_c)):
+            t0 = time.perf_counter()
+            fn()
+            if k >= 0:
+                t[name].append(time.perf_counter() - t0)
+    med = lambda v: float(np.median(v))
+    ms = lambda v: [round(1e3 * med(v), 3), round(1e3 * min(v), 3), round(1e3 * max(v), 3)]
+    found = [k for k in range(WINDOW_CANDS) if c_out[k].found]
+    err = [float(np.hypot(c_out[k].estimated_pose.x - truths[k][0], c_out[k].estimated_pose.y - truths[k][1])) for k in found]
+    drift = [float(np.hypot(nodes[k][0] - truths[k][0], nodes[k][1] - truths[k][1])) for k in range(WINDOW_CANDS)]
+    stats = ctx.icp_window_stats()
+    print(json.dumps(dict(line="window", halves=[hx, hy, ht], steps=list(WINDOW_STEPS), poses=n_poses, beams=len(ang),
+                          scans_per_ref=REF_SET_SCANS, timed_rounds=args.steps, same_bytes=same,
+                          a_refine_batch_ms_med_min_max=ms(t["a"]), b_window_scores_ms_med_min_max=ms(t["b"]),
+                          a_spread=round((max(t["a"]) - min(t["a"])) / med(t["a"]), 4),
+                          a_over_b=round(med(t["a"]) / med(t["b"]), 3),
+                          b_ns_per_pose_beam=round(1e9 * med(t["b"]) / (n_poses * len(ang)), 3),
+                          c_candidates=WINDOW_CANDS, c_detect_ms_med_min_max=ms(t["c"]),
+                          c_ms_per_candidate=round(1e3 * med(t["c"]) / WINDOW_CANDS, 3),
+                          c_ns_per_pose_beam=round(1e9 * med(t["c"]) / (WINDOW_CANDS * n_poses * len(ang)), 3),
+                          c_found=len(found), c_median_drift_m=round(float(np.median(drift)), 4),
+                          c_median_error_m=float(np.median(err)) if err else None,
+                          window_stats=list(stats))), flush=True)
+    rset.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--beams", type=int, default=1081)
@@ -282,12 +400,21 @@ def main():
     ap.add_argument("--ref-set", type=int, nargs="+", metavar="M",
                     help="instead of the lines above: per M, one lgs_icp_ref_set_create of M references x 10 scans "
                          "against M lgs_icp_ref_create calls, and lgs_loop_refine_icp per candidate (DESIGN.md 4.5d)")
+    ap.add_argument("--window", type=int, nargs=3, metavar=("HX", "HY", "HT"),
+                    help="instead of the lines above: the window search of (2 HX + 1) x (2 HY + 1) x (2 HT + 1) start "
+                         "poses, scored by the refine batch, by lgs_icp_ref_window_scores, and lgs_loop_detect_icp "
+                         "for 64 candidates (DESIGN.md 4.5e)")
     ap.add_argument("--step", choices=["gpu"], help=argparse.SUPPRESS)   # child mode
     args = ap.parse_args()
+    if args.window and (min(args.window) < 0 or max(args.window) > 512 or
+                        np.prod([2 * h + 1 for h in args.window]) > 1048576):
+        ap.error("--window: halves in 0 .. 512, at most 1048576 poses")
     if args.ref_set and min(args.ref_set) < 1:
         ap.error("--ref-set: at least one reference")
     if args.step:
-        if args.ref_set:
+        if args.window:
+            window_step(args)
+        elif args.ref_set:
             ref_set_step(args)
         else:
             gpu_step(args)
@@ -296,6 +423,8 @@ def main():
            str(args.lone), "--steps", str(args.steps), "--warmup", str(args.warmup), "--ref-scans", str(args.ref_scans)]
     if args.ref_set:
         cmd += ["--ref-set"] + [str(m) for m in args.ref_set]
+    if args.window:
+        cmd += ["--window"] + [str(h) for h in args.window]
     try:
         rc = subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
