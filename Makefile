@@ -30,6 +30,7 @@ cpptest: host oracle
 	$(MAKE) -C tests/cpp_icp_window
 	$(MAKE) -C tests/cpp_loop_search
 	$(MAKE) -C tests/cpp_hv
+	$(MAKE) -C tests/cpp_coarse_pair
 	$(MAKE) -C tests/cpp_loop
 	$(MAKE) -C tests/cpp_pg_cases
 
@@ -52,6 +53,7 @@ clean:
 	$(MAKE) -C tests/cpp_icp_window clean
 	$(MAKE) -C tests/cpp_loop_search clean
 	$(MAKE) -C tests/cpp_hv clean
+	$(MAKE) -C tests/cpp_coarse_pair clean
 	$(MAKE) -C tests/cpp_loop clean
 	$(MAKE) -C tests/cpp_pg_cases clean
 

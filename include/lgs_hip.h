@@ -201,6 +201,8 @@ int  lgs_abi_version(void);
 #define LGS_OPT_FAST_ROWS     37  /* 1 (default) = a lean batch's superblock pass forms a wave's 64 hit-point cells with a shorter fp64 chain (csrc/fast_cell.hpp) wherever every lane's cell is certified equal to the exact chain's and unguarded, and with the exact chain otherwise (bit-identical records); 0 = the exact chain always */
 #define LGS_OPT_HV_INZERO     38  /* 1 (default) = a thread of the superblock pass (k_super_hv) whose whole input footprint lies in precompute tiles that read all-(+0) inputs this call (k_hv_inzero: one 64-bit lane mask per set and wave) issues none of its loads; 0 = no mask, every thread loads (A/B inside one build, tests).  Batches of two or more maps only (a lone call is latency-bound and takes no mask); needs LGS_OPT_ZERO_TILES 1 */
 #define LGS_OPT_SELECT_LIST   41  /* batched pruned correlative chunks that take the kept-superblock work list (LGS_OPT_LANES_MIN_BATCH): the largest number of coarse blocks per match (K = angles x blocks per angle) up to which the refine candidates are selected from the listed superblocks' blocks alone, in one launch of one workgroup per match that also writes the dense list (k_select_list); above it, and with 0 = never, k_select rules on every coarse block and k_compact writes the dense list (the same bytes either way).  Default 524288, what the kernel's 64 KB of LDS hold (larger values mean the same) */
+#define LGS_OPT_LIST_ORDER    42  /* batched pruned correlative chunks that take the kept-superblock work list: 1 = the list is written superblock-major with the angles ascending within a superblock, and the edge angles ascending, by one workgroup per match with prefix sums (k_keep_ord: no atomics on the list, the same list every run; batches whose keep masks, 8 bytes per search angle, exceed 32 KB keep k_keep); 0 = k_keep appends each angle's kept superblocks with an atomic add, in the completion order of its workgroups.  The same entries, counters and records either way.  Default 1 */
+#define LGS_OPT_LIST_PAIRS    43  /* the same batches: 1 = the exact coarse pass gives a lane two neighbouring blocks of a superblock row and gathers both with one 16-byte load per beam, 8 listed superblocks per wave (k_coarse_list_p), wherever every pair's read stays inside the match's phase planes (csrc/coarse_pair.hpp); 0 = one block and one 8-byte load per lane, 4 superblocks per wave (k_coarse_list_c).  The same scores and flags either way.  Default 0 (measured slower: the exact coarse pass +24 % on the default workload) */
 #define LGS_OPT_POISON_WS     15/* diagnostics: 1 = fill every match workspace and record with 0xFF bytes before the batch runs (any read-before-write shows up) */
 int  lgs_ctx_set_option(lgs_ctx* ctx, int option, double value);
 
@@ -220,7 +222,11 @@ int  lgs_ctx_set_option(lgs_ctx* ctx, int option, double value);
  * selected blocks, ascending], 13 segcnt [nseg i32], 14 nsel [i32] followed
  * by dlist [K i32: the first nsel are the selected blocks, ascending; empty
  * when the batch's fine evaluator takes no dense list], 15 one i32: 1 when
- * k_select_list wrote the item's selection, 0 when k_select (+ k_compact) did. */
+ * k_select_list wrote the item's selection, 0 when k_select (+ k_compact) did.
+ * 16 cflag [K u8].  The kept-superblock work list (empty when the batch took
+ * none): 17 the item's entries [region i32, t << 6 | superblock: the first
+ * cnt[0] are listed], 18 its counters [16 i32: 0 entries, 1 edge angles],
+ * 19 its edge angles [Tmax i32: the first cnt[1] are listed]. */
 int  lgs_debug_item_buffer(lgs_ctx* ctx, int item, int which, void* out, size_t cap, size_t* bytes);
 
 /* Diagnostics: the device's restatements of glibc's sincos() (op 0: out[2i] =

@@ -37,6 +37,7 @@
 #include "loop_host.hpp"
 #include "fast_cell.hpp"
 #include "hv_zero.hpp"
+#include "coarse_pair.hpp"
 #include "sq_cost_stage.hpp"
 #include "ge_cost_device.hpp"
 
@@ -349,6 +350,18 @@ __device__ __forceinline__ void chk_coarse(const RtcsmPlan& pl, int b, int t, in
     }
     offchk_note(ok, 1, t, v, b);
 }
+// k_coarse_list_p: the pairs' second blocks too -- with an odd ncx the last
+// pair's second block is read and dropped, one cell past the window's row
+__device__ __forceinline__ void chk_coarse_pair(const RtcsmPlan& pl, int b, int t, int v)
+{
+    const long long all = (long long)pl.low_res * pl.low_res * pl.pstride;
+    bool ok = b >= 0 && b < all;
+    if (ok) {
+        const long long o = b % pl.pstride;
+        ok = o / pl.Wqp + pl.ncy <= pl.Hqp && o % pl.Wqp + ((pl.ncx + 1) & ~1) <= pl.Wqp;
+    }
+    offchk_note(ok, 3, t, v, b);
+}
 __device__ __forceinline__ void chk_super(const RtcsmPlan& pl, int c, int t, int v)
 {
     bool ok;
@@ -363,9 +376,11 @@ __device__ __forceinline__ void chk_super(const RtcsmPlan& pl, int c, int t, int
     offchk_note(ok, 2, t, v, c);
 }
 #define LGS_CHK_COARSE(pl, b, t, v) chk_coarse(pl, b, t, v)
+#define LGS_CHK_COARSE_PAIR(pl, b, t, v) chk_coarse_pair(pl, b, t, v)
 #define LGS_CHK_SUPER(pl, c, t, v) chk_super(pl, c, t, v)
 #else
 #define LGS_CHK_COARSE(pl, b, t, v) ((void)0)
+#define LGS_CHK_COARSE_PAIR(pl, b, t, v) ((void)0)
 #define LGS_CHK_SUPER(pl, c, t, v) ((void)0)
 #endif
 
@@ -1040,6 +1055,59 @@ __device__ __forceinline__ double seq_sum_from4(double s, int n, Fetch fetch, Ad
         add_batch(s, d, n - v0 - 3 * kPipe);
     }
     return s;
+}
+
+// seq_sum_from for a lane that owns two neighbouring cells (k_coarse_list_p):
+// one 16-byte gather per beam (the address is 8-byte aligned only), two sums,
+// each added strictly in beam order; the same depth and look-ahead (2 * kPipe)
+typedef double d2a8 __attribute__((ext_vector_type(2), aligned(8)));
+// (two arrays of doubles per buffer: an array of the vector type stays in scratch)
+struct PairBuf {
+    double x[kPipe], y[kPipe];
+};
+template <class Rec, class Fetch, class Addr>
+__device__ __forceinline__ void issue_batch2(int v0, Fetch& fetch, Addr& addr, PairBuf& buf)
+{
+    typedef const __attribute__((address_space(1))) d2a8 gd2a8_t;
+    Rec rc[kPipe];
+#pragma unroll
+    for (int j = 0; j < kPipe; ++j) rc[j] = fetch(v0 + j);
+#pragma unroll
+    for (int j = 0; j < kPipe; ++j) {
+        const d2a8 v = *(gd2a8_t*)addr(rc[j]);
+        buf.x[j] = v.x;
+        buf.y[j] = v.y;
+    }
+}
+__device__ __forceinline__ void add_batch2(double& s0, double& s1, const PairBuf& buf, int left)
+{
+    if (left >= kPipe) {
+#pragma unroll
+        for (int j = 0; j < kPipe; ++j) {
+            s0 += buf.x[j];
+            s1 += buf.y[j];
+        }
+    } else {
+#pragma unroll   // (constant indices: a run-time index would put the buffers in scratch)
+        for (int j = 0; j < kPipe; ++j)
+            if (j < left) {
+                s0 += buf.x[j];
+                s1 += buf.y[j];
+            }
+    }
+}
+template <class Rec, class Fetch, class Addr>
+__device__ __forceinline__ void seq_sum_from2(double& s0, double& s1, int n, Fetch fetch, Addr addr)
+{
+    PairBuf a, b;
+    issue_batch2<Rec>(0, fetch, addr, a);
+    for (int v0 = 0; v0 < n; v0 += 2 * kPipe) {
+        issue_batch2<Rec>(v0 + kPipe, fetch, addr, b);
+        add_batch2(s0, s1, a, n - v0);
+        if (v0 + kPipe >= n) break;
+        issue_batch2<Rec>(v0 + 2 * kPipe, fetch, addr, a);
+        add_batch2(s0, s1, b, n - v0 - kPipe);
+    }
 }
 
 // --------------------------------------------------------------------------
@@ -2178,6 +2246,98 @@ __global__ __launch_bounds__(64) void k_keep(Items items, WorkList W, DevTs dts)
     if (kp) W.sbl[(size_t)j * W.region + base + __popcll(bal & ((1ull << lane) - 1ull))] = t << 6 | lane;
 }
 
+// k_keep with the list in order (LGS_OPT_LIST_ORDER): one workgroup per item,
+// the same rule and the same counters, sbl superblock-major with the angles
+// ascending within a superblock, al ascending.  A beam's fine cell -- its
+// phase plane and lattice start -- often stays the same from one search angle
+// to the next, so entries that share a k_coarse_list wave then read the same
+// lines; k_keep's order is the completion order of its workgroups.  One
+// 64-bit keep mask per angle in dynamic LDS (the host takes k_keep when they
+// do not fit); wave w owns the angles [w, w + 1) * ceil(T / waves): it counts
+// them per superblock, prefix sums over (superblock, wave) give every (wave,
+// superblock) its first position, and a second walk writes the entries.  No
+// atomics on the list, and the same list every run.
+constexpr int kKeepOrdThreads = 1024;
+constexpr int kKeepOrdMaxT = 4096;   // 32 KB of masks
+__global__ __launch_bounds__(kKeepOrdThreads) void k_keep_ord(Items items, WorkList W, DevTs dts)
+{
+    const DtsScopeAll dts_scope(dts);
+    extern __shared__ unsigned long long s_keep[];   // T masks
+    constexpr int kW = kKeepOrdThreads / 64;
+    __shared__ int s_pos[kW][64];
+    const int j = blockIdx.x;
+    const MatchItem& it = items[j];
+    const RtcsmPlan& pl = it.pl;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int nsb2 = pl.nsbx * pl.nsby, T = pl.T;
+    double L = -INFINITY;
+#pragma unroll
+    for (int b = 0; b < kSeedCands; ++b) L = fmax(L, it.Lc[b]);
+    if (tid == 0) *it.Lp = L;
+    const int per = (T + kW - 1) / kW, t0 = min(wid * per, T), t1 = min(t0 + per, T);
+    int mine = 0;   // lane = superblock: kept angles of this wave's range
+    constexpr int kG = 8;   // angles whose bound reads are in flight together
+    for (int tg = t0; tg < t1; tg += kG) {   // wave-uniform
+        double bnd[kG];
+#pragma unroll
+        for (int g = 0; g < kG; ++g)
+            bnd[g] = (lane < nsb2 && tg + g < t1) ? gload(it.sbound + (size_t)(tg + g) * nsb2 + lane) : -INFINITY;
+#pragma unroll
+        for (int g = 0; g < kG; ++g) {
+            const bool kp = (bnd[g] > pl.thr) && bnd[g] >= L;   // (-inf: neither)
+            const unsigned long long bal = __ballot(kp);
+            if (lane == 0 && tg + g < t1) s_keep[tg + g] = bal;
+            mine += kp ? 1 : 0;
+        }
+    }
+    s_pos[wid][lane] = mine;
+    __syncthreads();
+    if (wid == 0) {
+        int part[kW], tot = 0;
+#pragma unroll
+        for (int w = 0; w < kW; ++w) {
+            part[w] = tot;
+            tot += s_pos[w][lane];
+        }
+        int incl = tot;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int u = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += u;
+        }
+#pragma unroll
+        for (int w = 0; w < kW; ++w) s_pos[w][lane] = incl - tot + part[w];
+        // the blocks the listed superblocks hold (k_keep's count)
+        const int nsbx = max(pl.nsbx, 1), a = lane % nsbx, b = lane / nsbx;
+        unsigned long long nb =
+            lane < nsb2 ? (unsigned long long)tot * (unsigned long long)(min(kSB, pl.ncx - kSB * a) * min(kSB, pl.ncy - kSB * b)) : 0ull;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) nb += __shfl_xor(nb, off, 64);
+        if (lane == 63) {
+            W.cnt[16 * j] = incl;
+            if (nb) atomicAdd(&it.rec->coarse_evals, nb);
+        }
+        // the edge angles that keep something, ascending
+        int na = 0;
+        for (int tb = 0; tb < T; tb += 64) {   // wave-uniform
+            const int t = tb + lane;
+            const bool ed = t < T && s_keep[t] != 0ull && it.tedge[t] == it.gen;
+            const unsigned long long bal = __ballot(ed);
+            if (ed) W.al[(size_t)j * W.tmax + na + __popcll(bal & ((1ull << lane) - 1ull))] = t;
+            na += __popcll(bal);
+        }
+        if (lane == 0) W.cnt[16 * j + 1] = na;
+    }
+    __syncthreads();
+    if (lane < nsb2) {
+        int pos = s_pos[wid][lane];
+        int* __restrict__ sbl = W.sbl + (size_t)j * W.region;
+        for (int t = t0; t < t1; ++t)
+            if ((s_keep[t] >> lane) & 1ull) sbl[pos++] = t << 6 | lane;
+    }
+    __syncthreads();   // (device timing: thread 0 stamps the end after every wave's walk)
+}
+
 // Inclusive prefix of the items' counters `which` over lanes 0..n-1 (every
 // lane of the wave computes it); returns the total.
 __device__ __forceinline__ int list_prefix(const WorkList& W, int which, int n, int& c)
@@ -2323,6 +2483,132 @@ __global__ __launch_bounds__(64) void k_coarse_list_c(Items items, WorkList W, i
     }
 }
 
+// k_coarse_list_c with paired lanes (LGS_OPT_LIST_PAIRS): a lane owns blocks
+// (jx, jy) and (jx + 1, jy), jx even inside the superblock -- adjacent doubles
+// of a plane row -- and gathers both with one 16-byte load per beam: half the
+// gather instructions, addresses, LDS row reads and pointer selects for the
+// same bytes.  8 lanes make a superblock, 8 listed superblocks a wave; the
+// XCD split works in units of 8 entries.  Each block's sum is still added
+// strictly in beam order (seq_sum_from2), so cscore is bit for bit
+// k_coarse_list_c's.  With an odd ncx the last pair's second block does not
+// exist: its read lands in the plane row's margin (coarse_pair_read_inside,
+// the host's condition for this kernel) and its sum is dropped.  `zero` has
+// 16 readable zero bytes (the context's zero cell is 256).
+#ifndef LGS_LCP
+#define LGS_LCP 128
+#endif
+constexpr int kLCP = LGS_LCP;   // beams per staged chunk (8 rows: 4 KB of LDS per wave at 128)
+constexpr int kLCPPad = 2 * kPipe;
+static_assert(kLCP % 64 == 0, "whole waves per chunk row");
+__global__ __launch_bounds__(64) void k_coarse_list_p(Items items, WorkList W, int n, const double* __restrict__ zero, DevTs dts)
+{
+    const DtsScope dts_scope(dts);
+    __shared__ int s_cb[8][kLCP + kLCPPad];
+    const int lane = threadIdx.x, g8 = lane >> 3, m = lane & 7;
+    int c;
+    const int total = list_prefix(W, 0, n, c);
+    const bool lean = items[0].lean != 0;   // the batch's items all run lean or none
+    constexpr int kOff = -(1 << 30);
+    constexpr int PER = kLCP / 64;
+#if LGS_LIST_XCD
+    // XCD x takes the x-th eighth of the list's octets (k_coarse_list_c)
+    const int no = (total + 7) >> 3, xcd = blockIdx.x & 7, per = gridDim.x >> 3;
+    const int oe = (int)(((long long)no * (xcd + 1)) >> 3);
+    for (int od = (int)(((long long)no * xcd) >> 3) + (int)(blockIdx.x >> 3); od < oe; od += per) {
+        const int e0 = 8 * od;   // wave-uniform
+#else
+    for (int e0 = 8 * blockIdx.x; e0 < total; e0 += 8 * gridDim.x) {   // wave-uniform
+#endif
+        const int e = e0 + g8;
+        const bool has = e < total;
+        int j = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int jq = __popcll(__ballot(lane < n && c <= e0 + q));
+            if (g8 == q) j = jq;
+        }
+        if (!has) j = 0;
+        const int cprev = __shfl(c, max(j - 1, 0), 64);
+        const int before = j > 0 ? cprev : 0;
+        const MatchItem& it = items[j];
+        const RtcsmPlan& pl = it.pl;
+        const int ent = has ? W.sbl[(size_t)j * W.region + (e - before)] : 0;
+        const int t = ent >> 6, sb = ent & 63;
+        const int Nv = has ? pl.Nv : 0;
+        const int* __restrict__ cbr = it.cbase + (size_t)t * pl.Nv;
+        int nmax = Nv;
+#pragma unroll
+        for (int off = 8; off < 64; off <<= 1) nmax = max(nmax, __shfl_xor(nmax, off, 64));
+        const int nsbx = max(pl.nsbx, 1);
+        const int jx = kSB * (sb % nsbx) + 2 * (m & 1), jy = kSB * (sb / nsbx) + (m >> 1);
+        const bool active = has && jx < pl.ncx && jy < pl.ncy;   // the pair's first block exists
+        const double* __restrict__ lane_base = it.cmap + (active ? jy * pl.Wqp + jx : 0);
+        int pre[8][PER];
+        auto fetch_chunk = [&](int v0) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int nq = __shfl(Nv, 8 * q, 64);
+                if (lean) {   // the group's row formed here (lean_cell), its item and angle wave-uniform
+                    const int jq = __builtin_amdgcn_readfirstlane(__shfl(j, 8 * q, 64));
+                    const int tq = __builtin_amdgcn_readfirstlane(__shfl(t, 8 * q, 64));
+                    const MatchItem& iq = items[jq];
+#pragma unroll
+                    for (int i = 0; i < PER; ++i) {
+                        const int v = v0 + lane + 64 * i;
+                        pre[q][i] = v < nq ? lean_coarse_base(iq, tq, v) : kOff;
+                    }
+                    continue;
+                }
+                const int* row = (const int*)__shfl((unsigned long long)cbr, 8 * q, 64);
+#pragma unroll
+                for (int i = 0; i < PER; ++i) {
+                    const int v = v0 + lane + 64 * i;
+                    pre[q][i] = v < nq ? gload(row + v) : kOff;   // past a row: the zero cell
+                }
+            }
+#ifdef LGS_CHECK_OFFSETS
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int jq = __builtin_amdgcn_readfirstlane(__shfl(j, 8 * q, 64));
+                const int tq = __builtin_amdgcn_readfirstlane(__shfl(t, 8 * q, 64));
+                const int nq = __shfl(Nv, 8 * q, 64);
+#pragma unroll
+                for (int i = 0; i < PER; ++i) {
+                    const int v = v0 + lane + 64 * i;
+                    if (v < nq) LGS_CHK_COARSE_PAIR(items[jq].pl, pre[q][i], tq, v);
+                }
+            }
+#endif
+        };
+        fetch_chunk(0);
+        double sum0 = 0.0, sum1 = 0.0;
+        for (int v0 = 0; v0 < nmax; v0 += kLCP) {   // wave-uniform
+            // one wave: its LDS operations run in order, so the previous
+            // chunk's reads are done before these writes
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+#pragma unroll
+                for (int i = 0; i < PER; ++i) s_cb[q][lane + 64 * i] = pre[q][i];
+                if (lane < kLCPPad) s_cb[q][kLCP + lane] = kOff;   // seq_sum's look-ahead
+            }
+            if (v0 + kLCP < nmax) fetch_chunk(v0 + kLCP);
+            const int cnt = min(kLCP, nmax - v0);
+            const int* __restrict__ my = s_cb[g8];
+            seq_sum_from2<int>(sum0, sum1, cnt, [&](int v) { return my[v]; },
+                               [&](const int& cc) { return (active && cc != kOff) ? lane_base + cc : zero; });
+        }
+        if (active) {
+            const long long k = (long long)t * pl.P + (long long)jx * pl.ncy + jy;
+            it.cscore[k] = sum0;
+            it.cflag[k] = 0;
+            if (jx + 1 < pl.ncx) {   // block (jx + 1, jy)
+                it.cscore[k + pl.ncy] = sum1;
+                it.cflag[k + pl.ncy] = 0;
+            }
+        }
+    }
+}
+
 // The unsafe test of the listed edge angles (k_keep), one angle at a time per
 // workgroup (grid-stride).
 __global__ __launch_bounds__(64 * kLaneWaves) void k_unsafe_list(Items items, WorkList W, int n,
@@ -2402,7 +2688,6 @@ __device__ void eval_block(const RtcsmPlan& pl, const double* __restrict__ grid,
 // register copies).  Beam indices of the angle row are staged in LDS first.
 // Ties resolve to the smallest reference order index o = xo*LR + yo.
 constexpr int kMaxChunks = 32;   // transposed evaluator handles Nv <= 2048
-typedef double d2a8 __attribute__((ext_vector_type(2), aligned(8)));
 
 
 // row >= 0 (row split): the workgroup is one wave that evaluates block row
@@ -4632,6 +4917,12 @@ inline bool select_list_fits(const lgs_ctx* ctx, const BatchShape& B)
     return B.wl.cnt && (long long)B.Tmax * B.P <= std::min(ctx->select_list, kSelListMaxK);
 }
 
+// The work list in order (k_keep_ord; LGS_OPT_LIST_ORDER): the batch's keep
+// masks, one 64-bit word per angle, fit the kernel's LDS
+inline bool list_ordered(const lgs_ctx* ctx, const BatchShape& B)
+{
+    return ctx->list_order && B.wl.cnt && B.Tmax <= kKeepOrdMaxT;
+}
 // Per-item workspace: one contiguous region per item carved from S_BATCH_WS
 // (sized for the batch's largest plan), field offsets below.
 struct ItemLayout {
@@ -4707,6 +4998,23 @@ void bind_workspace(MatchItem& it, char* base, const ItemLayout& L, int frows)
 inline size_t plane_bytes(const RtcsmPlan& pl)
 {
     return align256(sizeof(double) * (size_t)pl.low_res * pl.low_res * (size_t)pl.pstride);
+}
+// Paired lanes (k_coarse_list_p): every 16-byte read of a plan's pairs, the
+// dropped second block of an odd ncx included, stays inside the set's fp64
+// plane allocation (coarse_pair.hpp); k_coarse_list_c where it does not.
+inline bool coarse_pairs_ok(const RtcsmPlan& pl)
+{
+    const lgs::CoarsePairGeom g = { pl.low_res, pl.Wq, pl.Hq, pl.M, pl.Wqp, pl.Hqp, pl.ncx, pl.ncy,
+                                    pl.pstride, (long long)(plane_bytes(pl) / sizeof(double)) };
+    return lgs::coarse_pair_read_inside(g);
+}
+// LGS_OPT_LIST_PAIRS: the batch's coarse pass is k_coarse_list_p
+inline bool list_paired(const lgs_ctx* ctx, const std::vector<MatchItem>& items)
+{
+    if (!ctx->list_pairs) return false;
+    for (const auto& it : items)
+        if (!coarse_pairs_ok(it.pl)) return false;
+    return true;
 }
 // the planes' fp16 round-up copies (the superblock pass's input), right after
 // each set's fp64 planes: a fixed place per set, so their zero margins stay zero
@@ -5351,13 +5659,19 @@ void enqueue_items(lgs_ctx* ctx, const BatchShape& B, Items d_items, const std::
         wl = n >= ctx->lanes_min_batch && B.wl.cnt && !ctx->skipped(K_COARSE);
         if (wl) {
             const int tk = ctx->timing_begin(K_COARSE_AUX, 8.0 * (double)B.Tmax * B.nsb2 * n);   // bound reads
-            hipLaunchKernelGGL(k_keep, dim3(B.Tmax, n), dim3(64), 0, st, d_items, B.wl, ctx->dts(tk));
+            if (list_ordered(ctx, B))
+                hipLaunchKernelGGL(k_keep_ord, dim3(n), dim3(kKeepOrdThreads), sizeof(unsigned long long) * (size_t)B.Tmax, st,
+                                   d_items, B.wl, ctx->dts(tk));
+            else
+                hipLaunchKernelGGL(k_keep, dim3(B.Tmax, n), dim3(64), 0, st, d_items, B.wl, ctx->dts(tk));
             ctx->timing_end(tk);
             LGS_HIP_CHECK(hipGetLastError());
         }
         const int tok = ctx->timing_begin(K_COARSE, 8.0 * beams_K);
         if (tok >= 0) ctx->pending[tok].coarse_evals = true;   // algorithmic bytes from the records
         if (ctx->skipped(K_COARSE)) {
+        } else if (wl && list_paired(ctx, items)) {
+            hipLaunchKernelGGL(k_coarse_list_p, dim3(kListWaves), dim3(64), 0, st, d_items, B.wl, n, zero, ctx->dts(tok));
         } else if (wl) {
             hipLaunchKernelGGL(k_coarse_list_c, dim3(kListWaves), dim3(64), 0, st, d_items, B.wl, n, zero, ctx->dts(tok));
         } else {
@@ -5869,6 +6183,15 @@ void launch_matches(lgs_ctx* ctx, const lgs_rtcsm_params* params, const lgs_cost
         d.bytes[10] = dps ? dps->hv_in_bytes : 0;
         d.buf[11] = dps ? dps->hv_out : nullptr;
         d.bytes[11] = dps ? dps->hv_out_bytes : 0;
+        d.buf[16] = ij.cflag;
+        d.bytes[16] = B.small ? 0 : (size_t)q.K;
+        const bool dwl = B.wl.cnt && n >= ctx->lanes_min_batch;   // the work list (its last writer: this batch)
+        d.buf[17] = dwl ? B.wl.sbl + (size_t)j * B.wl.region : nullptr;
+        d.bytes[17] = dwl ? sizeof(int) * (size_t)B.wl.region : 0;
+        d.buf[18] = dwl ? B.wl.cnt + 16 * (size_t)j : nullptr;
+        d.bytes[18] = dwl ? sizeof(int) * 16 : 0;
+        d.buf[19] = dwl ? B.wl.al + (size_t)j * B.wl.tmax : nullptr;
+        d.bytes[19] = dwl ? sizeof(int) * (size_t)B.wl.tmax : 0;
         d.gen = ij.gen;
         if (!B.small) {   // the selection (k_match_small makes none)
             d.list = ij.list;
@@ -6251,11 +6574,11 @@ void cost_summaries(lgs_ctx* ctx, const lgs_grid* grid, const lgs_cost_ge_params
 
 extern "C" int lgs_debug_item_buffer(lgs_ctx* ctx, int item, int which, void* out, size_t cap, size_t* bytes)
 {
-    if (!ctx || which < 0 || which >= 16 || item < 0) return LGS_ERR_INVALID_ARG;
+    if (!ctx || which < 0 || which >= 20 || item < 0) return LGS_ERR_INVALID_ARG;
     return guarded(ctx, [&] {
         LGS_REQUIRE((size_t)item < ctx->dbg.size(), "no such item in the last correlative batch");
         const lgs_ctx::DbgItem& d = ctx->dbg[(size_t)item];
-        if (which >= 12) {   // the selection: two device buffers (14) or a host value (15)
+        if (which >= 12 && which < 16) {   // the selection: two device buffers (14) or a host value (15)
             const void* src[2] = { nullptr, nullptr };
             size_t sz[2] = { 0, 0 };
             const int sel = d.sel_list;

@@ -566,6 +566,8 @@ extern "C" int lgs_ctx_set_option(lgs_ctx* ctx, int option, double value)
         if (!(value >= 0.0)) return LGS_ERR_INVALID_ARG;
         ctx->select_list = (long long)std::min(value, 9.0e18);
         return LGS_OK;
+    case LGS_OPT_LIST_ORDER: ctx->list_order = value != 0.0; return LGS_OK;
+    case LGS_OPT_LIST_PAIRS: ctx->list_pairs = value != 0.0; return LGS_OK;
     case LGS_OPT_SEED_WIDE:
         if (!(value >= 0.0 && value <= 16.0)) return LGS_ERR_INVALID_ARG;
         ctx->seed_wide = (int)value;

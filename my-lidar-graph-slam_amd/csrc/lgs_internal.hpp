@@ -382,6 +382,8 @@ struct lgs_ctx {
     bool post_records = true;    // records written to pinned memory by k_post + a flag (LGS_OPT_POST_RECORDS)
     long long copies_direct = 0, copies_staged = 0;   // lgs_debug_copy_counters
     long long select_list = 524288;   // work-list batches of at most this many keys per item select from the list (k_select_list; LGS_OPT_SELECT_LIST, 0 = never)
+    bool list_order = true;      // the work list superblock-major, angles ascending (k_keep_ord; LGS_OPT_LIST_ORDER; measured: k_coarse 0.140 -> 0.123 ms per 64 one-stream, headline +4.4 %)
+    bool list_pairs = false;     // two blocks per lane, 16-byte gathers (k_coarse_list_p; LGS_OPT_LIST_PAIRS; measured: k_coarse 0.140 -> 0.174 ms per 64 one-stream, 0.123 -> 0.158 with the ordered list)
     int lanes_min_batch = 2;     // pruned coarse stage: the work list (k_coarse_list) from this batch size on (LGS_OPT_LANES_MIN_BATCH)
     long long ray_chunk_keys = 1LL << 28;  // ray-cast keys per emit/sort/apply pass (LGS_OPT_RAY_CHUNK_KEYS)
     // Stamps come from one process-wide counter: a context's scratch may be
@@ -396,8 +398,8 @@ struct lgs_ctx {
     bool poison_ws = false;
     // intermediates of every item of the last correlative batch (lgs_debug_item_buffer)
     struct DbgItem {
-        const void* buf[12];
-        size_t bytes[12];
+        const void* buf[20];   // 12-15 unused (the selection below); 16-19: cflag and the work list
+        size_t bytes[20];
         int gen;
         // the selection (which 12-15): list, segcnt, nsel + dlist (null: no dense list), and which kernel wrote them
         const int *list, *segcnt, *nsel, *dlist;

@@ -58,6 +58,8 @@ KERNEL_IDS = ["k_project", "k_coarse", "k_seed", "k_select", "k_fine", "k_replay
 MORE_KERNEL_IDS = ["k_loop_search"]
 LGS_OPT_LOOP_SEARCH_MIN_PAIRS = 39  # lgs_loop_search_nearest: hint x position pairs below which the host loop runs (0: always the device)
 LGS_OPT_LOOP_SEARCH_GROUP = 40      # tests: walk positions per workgroup group of the search (0: chosen per call)
+LGS_OPT_LIST_ORDER = 42             # work-list batches: the list superblock-major, angles ascending (k_keep_ord; 0: k_keep's atomics)
+LGS_OPT_LIST_PAIRS = 43             # work-list batches: two blocks per lane, 16-byte gathers (k_coarse_list_p; 0: k_coarse_list_c)
 LGS_OPT_SELECT_LIST = 41            # work-list batches: largest K selected from the kept-superblock list (k_select_list; 0: never)
 
 
@@ -1404,7 +1406,10 @@ class Context:
                      "hv_inmask": (10, np.uint64), "hv_outmask": (11, np.uint64),
                      # the selection: list [nseg, 1024], segcnt [nseg], [nsel, dlist...], [1 = k_select_list wrote it]
                      "sel_list": (12, np.int32), "sel_segcnt": (13, np.int32), "sel_dense": (14, np.int32),
-                     "sel_by_list": (15, np.int32)}
+                     "sel_by_list": (15, np.int32),
+                     # cflag [K]; the work list: entries t << 6 | sb, [entries, edge angles, ...], edge angles
+                     "cflag": (16, np.uint8), "wl_sbl": (17, np.int32), "wl_cnt": (18, np.int32),
+                     "wl_al": (19, np.int32)}
 
     def debug_buffer(self, name: str, item: int = 0) -> np.ndarray:
         """Diagnostics: an intermediate buffer of one item of the last
